@@ -4,12 +4,15 @@
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N ranks, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR                 (also writes what the last timed step computed, see dump_outputs)
+    python bench.py ... --full                             (also the side legs: other precisions and configurations, roofline, CPU baseline, ...)
 
 Workload (BASELINE.json configs[1] / configs[3]): CubeNET(238, 1, first_depth=64, bilinear=False) in train
 mode on synthetic 608x968x238 fp32 cubes, per-rank batch 2 (params_HyperPRI.py:178), loss =
 BCEWithLogitsLoss (params_HyperPRI.py:223), one step = forward + loss + backward (+ gradient all-reduce
 for N > 1; optimizer excluded).  Inputs are generated on the device by the counter-based
-generator before the timed region.  Rank 0 prints ONE JSON line.
+generator before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and
+prints the line; every leg and check beside the headline loop runs with --full only.
 """
 import argparse
 import json
@@ -45,6 +48,25 @@ def synth_init_(net):
             if p.dim() >= 2:
                 fan_in = p.shape[1] * int(math.prod(p.shape[2:]))
             synth_fill_(p.data, 1000 + k, mode=2, scale=1.0 / math.sqrt(fan_in))
+
+
+DUMP_MAX_PER_TENSOR = 1 << 18      # elements; 82 gradient tensors + logits stay near 22 MB
+
+
+def dump_outputs(out_dir, net, logits, loss):
+    """What a caller of the timed step receives from its last run, as float32 .npy files in ``out_dir``: ``logits.npy``, ``loss.npy``
+    and ``grad.<parameter name>.npy``.  A gradient larger than DUMP_MAX_PER_TENSOR elements is written as a fixed sample of its flat
+    elements (ascending indices drawn with seed = the parameter's position), so that two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "logits.npy"), logits.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(float(loss.detach()), dtype=np.float32))
+    for k, (name, p) in enumerate(net.named_parameters()):
+        g = p.grad.detach().reshape(-1)
+        if g.numel() > DUMP_MAX_PER_TENSOR:
+            idx = np.sort(np.random.default_rng(k).choice(g.numel(), DUMP_MAX_PER_TENSOR, replace=False))
+            g = g[torch.from_numpy(idx).to(g.device)]
+        np.save(os.path.join(out_dir, f"grad.{name}.npy"), g.float().cpu().numpy())
 
 
 def _lib_stamp():
@@ -340,6 +362,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg and check beside the headline loop (training-shaped loop, optimizer step, other precision "
+                         "modes, predict path, per-kernel roofline, BASELINE's other configurations, CPU baseline, stock DDP and the "
+                         "reduced-gradient check at N > 1); the --no-* options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits, loss and parameter gradients of the last one to DIR/*.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true", help="skip the per-kernel HIP-event pass")
     ap.add_argument("--no-optimizer-leg", action="store_true",
@@ -363,11 +391,18 @@ def main():
                     help="N > 1: cap RCCL's channels (NCCL_MAX_NCHANNELS, set before the communicator is created): every channel is a workgroup "
                          "that holds part of a compute unit while a bucket's all-reduce runs beside the backward (tools/cu_share_probe.py); 0 = RCCL's default")
     ap.add_argument("--stock-ddp", action="store_true",
-                    help="with --force-sync at N = 1: also run the stock-DistributedDataParallel leg that every N > 1 run takes")
+                    help="with --force-sync --full at N = 1: also run the stock-DistributedDataParallel leg that every N > 1 run with --full takes")
     ap.add_argument("--no-stock-ddp", action="store_true", help="N > 1: skip the stock-DistributedDataParallel leg")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher rehearsal: the ranks run a gloo all-reduce on the CPU instead of the GPU workload")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does what the headline figure needs and nothing else
+        args.no_training_shaped = args.no_optimizer_leg = args.no_predict_leg = args.no_roofline = True
+        args.no_configs = args.no_cpu_baseline = args.no_stock_ddp = True
+        args.bf16_steps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args, sys.argv[1:])       # before anything touches the GPU
@@ -428,7 +463,7 @@ def main():
     # kernels are deterministic and the parameters frozen, so over gloo the two are bit-equal and over RCCL equal to its
     # summation order) -- ranks that merely hold EQUAL gradients say nothing about a stale slab or an early hand-over
     plain_flat = None
-    if use_pg and world > 1:
+    if use_pg and world > 1 and args.full:
         crit(net(x), mask).backward()
         torch.cuda.synchronize()
         plain_flat = torch.cat([p.grad.detach().reshape(-1) for p in net.parameters()])
@@ -440,13 +475,14 @@ def main():
         for p in net.parameters():
             p.grad = None
         if fused_loss:
-            _, loss = HP.forward_loss(net, x, mask)     # same loss; computed inside the head's kernels
+            pred, loss = HP.forward_loss(net, x, mask)     # same loss; computed inside the head's kernels
         else:
-            loss = crit(net(x), mask)
+            pred = net(x)
+            loss = crit(pred, mask)
         loss.backward()
         if sync is not None:
             sync.finish()
-        return loss
+        return pred, loss
 
     def fence():
         if use_pg:
@@ -493,7 +529,8 @@ def main():
     mallocs0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        logits = None                     # released before the next forward (holding it would take a second logits buffer)
+        logits, loss = step()
     fence()
     dt = time.perf_counter() - t0
     settle["device_mallocs_in_timed_region"] = int(torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - mallocs0)   # 0 = the pool was grown
@@ -502,6 +539,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_val = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, logits, loss)
+    del logits
     grad_sync = None
     if sync is not None:
         ov = sync.overlap_ms()           # last timed step: per bucket, all-reduce issue -> finish() return (stream time)
@@ -531,7 +571,7 @@ def main():
         grad_sync = {"backend": "gloo on one GPU (REHEARSAL, not a measurement)" if one_gpu else "nccl (RCCL)",
                      "max_rel_err": max_rel_err,
                      "max_rel_err_is": "max over parameter tensors and ranks of max|reduced gradient - mean of the ranks' plain-loop HIP "
-                                       "gradients| / max|mean| (0.0 = bit-equal; null at N = 1)",
+                                       "gradients| / max|mean| (0.0 = bit-equal; null at N = 1 and without --full)",
                      "ranks_hold_equal_gradients": equal, "grad_mb": round(sum(b.flat.numel() for b in sync.buckets) * 4 / 2 ** 20, 1),
                      "gradients_written_in_place": True, "overlap": ov, "buckets_issued_by": dict(sync.issued),
                      # what bounds the compute units the collective's kernels hold beside the backward (RCCL reads these when the
@@ -559,7 +599,7 @@ def main():
         mall_t = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
         tt = time.perf_counter()
         for _ in range(args.steps):
-            loss_t = step(); opt.step()
+            _, loss_t = step(); opt.step()
         fence()
         dtt = time.perf_counter() - tt
         if world > 1:
@@ -620,7 +660,7 @@ def main():
         m0 = torch.cuda.memory_stats(dev).get("num_device_alloc", 0)
         tb = time.perf_counter()
         for _ in range(args.bf16_steps):
-            lossb = step()
+            _, lossb = step()
         fence()
         dtb = time.perf_counter() - tb
         if world > 1:
@@ -854,7 +894,7 @@ def main():
         value = cubes / dt
         out = {
             "metric": "HSI cubes/sec (608x968x238) fwd+bwd", "value": round(value, 4), "unit": "cubes/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             # the arithmetic type of `value`: fp32 MFMA unless the caller switched the package default (HPRI_PRECISION), which
             # the line then says instead of claiming f32

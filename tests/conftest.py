@@ -2,6 +2,7 @@ import os
 import sys
 
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -17,6 +18,17 @@ def pytest_configure(config):
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN
+
+
+@pytest.fixture
+def fixture_threads():
+    """torch's CPU thread count of the fixture captures (torch.set_num_threads(8) in tests/golden/make_golden*.py): CPU reductions
+    sum in an order that depends on it, and the oracle tests compare values that are rounding noise (e.g. the gradient of a
+    convolution's bias ahead of a training-mode BatchNorm) against the captured ones."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
 
 
 # Parity margins observed by the GPU tests (max error / tolerance per check), written to gpurun_out/parity_margins.json

@@ -10,6 +10,7 @@ import torch
 
 from oracle import hyperpri_oracle as O
 
+pytestmark = pytest.mark.usefixtures("fixture_threads")
 G = os.path.join(os.path.dirname(__file__), "golden")
 TOL = dict(rtol=1e-5, atol=1e-6)
 

@@ -11,6 +11,7 @@ import torch
 
 from oracle import hyperpri_oracle as O
 
+pytestmark = pytest.mark.usefixtures("fixture_threads")
 G = os.path.join(os.path.dirname(__file__), "golden")
 
 

@@ -2,7 +2,7 @@
 # A/B of one environment switch on the bench step, interleaved (A B A B) in fresh processes: value + ms per step of the fp32 and the bf16 mode.
 # usage: tools/ab_env.sh VAR=value [tag]
 R=${GRAFT_REPO_ROOT:-/root/repo}; KV=$1; TAG=${2:-ab_env}; OUT=$R/gpurun_out/$TAG.txt; : > $OUT
-A="--steps 20 --warmup 5 --no-cpu-baseline --no-optimizer-leg --no-training-shaped --no-roofline --no-configs --bf16-steps 20"
+A="--full --steps 20 --warmup 5 --no-cpu-baseline --no-optimizer-leg --no-training-shaped --no-roofline --no-configs --bf16-steps 20"
 for i in 1 2; do
   for arm in base $KV; do
     if [ "$arm" = base ]; then E=""; else E="$KV"; fi

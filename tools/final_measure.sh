@@ -27,12 +27,12 @@ elif [ "$PART" = 2 ]; then
   timeout -k 10 400 python tools/dice_parity.py 14 20 ${TAG} fp32 > $G/${TAG}_dice_fp32.log 2>&1; echo "dice fp32 rc $?"; tail -1 $G/${TAG}_dice_fp32.log | cut -c1-300
   timeout -k 10 400 python tools/dice_parity.py 14 20 ${TAG}_bf16 bf16 > $G/${TAG}_dice_bf16.log 2>&1; echo "dice bf16 rc $?"; tail -1 $G/${TAG}_dice_bf16.log | cut -c1-300
   timeout -k 10 300 python tools/dice_parity.py 14 20 ${TAG}_f16 f16 > $G/${TAG}_dice_f16.log 2>&1; echo "dice f16 rc $?"; tail -1 $G/${TAG}_dice_f16.log | cut -c1-300
-  timeout -k 10 500 python bench.py > $G/${TAG}_bench_final.json 2> $G/${TAG}_bench_final.err; echo "bench rc $?"
+  timeout -k 10 500 python bench.py --full > $G/${TAG}_bench_final.json 2> $G/${TAG}_bench_final.err; echo "bench rc $?"
 else
   timeout -k 10 300 python tools/ddp_stock_bench.py > $G/${TAG}_ddp_stock_one_rank.json 2> $G/${TAG}_ddp_stock.err; echo "stock ddp rc $?"
   timeout -k 10 200 python tools/predict_bench.py 4 > $G/${TAG}_predict_ingest.json 2> $G/${TAG}_predict.err; echo "predict rc $?"
   for k in bf16 f16; do timeout -k 10 120 python tools/ingest_conv_bench.py $k 2>/dev/null; done > $G/${TAG}_ingest_conv.jsonl; echo "ingest conv rc $?"
-  timeout -k 10 300 python bench.py --force-sync --stock-ddp --no-configs --no-cpu-baseline > $G/${TAG}_force_sync_stock.json 2> $G/${TAG}_force_sync_stock.err; echo "force-sync bench rc $?"
+  timeout -k 10 300 python bench.py --full --force-sync --stock-ddp --no-configs --no-cpu-baseline > $G/${TAG}_force_sync_stock.json 2> $G/${TAG}_force_sync_stock.err; echo "force-sync bench rc $?"
   bash tools/prof_c3.sh bf16 ${TAG}_c3_bf16_final > /dev/null 2>&1; echo "c3 profile rc $?"
   bash tools/pmc_cmd.sh ${TAG}ig tools/ingest_conv_bench.py bf16 > $G/${TAG}_ig_pmc.log 2>&1; echo "ingest conv pmc rc $?"    # then: python tools/pmc_traffic.py gpurun_out/${TAG}ig ${TAG}_ingest_conv
 fi
