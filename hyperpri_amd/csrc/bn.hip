@@ -218,7 +218,9 @@ __global__ void bn_apply_relu_kernel(const float* __restrict__ x, int x_cs, int 
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (in_f) {
       const float4 v = bn_load_x4<XB>(x, p * x_cs + x_coff + c);
-      o.x = v.x * sc[0] + sh[0]; o.y = v.y * sc[1] + sh[1]; o.z = v.z * sc[2] + sh[2]; o.w = v.w * sc[3] + sh[3];
+      // pad channels are selected as zeros, not computed as x * 0 + 0: a NaN / inf the producer left there must not pass
+      o.x = (c + 0 < C) ? v.x * sc[0] + sh[0] : 0.f; o.y = (c + 1 < C) ? v.y * sc[1] + sh[1] : 0.f;
+      o.z = (c + 2 < C) ? v.z * sc[2] + sh[2] : 0.f; o.w = (c + 3 < C) ? v.w * sc[3] + sh[3] : 0.f;
       if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
       if (y != nullptr) *reinterpret_cast<float4*>(y + p * y_cs + y_coff + c) = o;
     }
