@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 from . import engine as _E
-from .engine import Act, Tape, _require_cuda, join_side, scale_tensors_
+from .engine import Act, Tape, _require_cuda, join_side
 
 
 def _as4d(t: torch.Tensor) -> torch.Tensor:
@@ -300,7 +300,7 @@ class _HipFn(torch.autograd.Function):
                 res.append(tape.param_grads.pop(id(p), None) if (need[ctx.n_in + j] and not sunk) else None)
                 tape.delivered.add(id(p))
             if tape.gscale != 1.0:                 # half-precision mode: the loss scale leaves the parameter gradients here
-                scale_tensors_([g for g in res[1:] if g is not None], 1.0 / tape.gscale)
+                tape.unscale_([g for g in res[1:] if g is not None])
             ctx.acts = ctx.params = ctx.out_act = ctx.holder = None
             return (None, None, None, None, *res)
         n_act = len(res)
@@ -311,8 +311,7 @@ class _HipFn(torch.autograd.Function):
         if tape.gscale != 1.0:
             # half-precision mode: the loss scale leaves the parameter gradients here (gradients in a GradSync bucket lost it before
             # their hand-over: engine.Tape.backward); an input gradient carries it too
-            scale_tensors_([g for g in res[n_act:] if g is not None] + [g.contiguous() for g in res[:n_act] if g is not None and g.is_contiguous()],
-                           1.0 / tape.gscale)
+            tape.unscale_([g for g in res[n_act:] if g is not None] + [g.contiguous() for g in res[:n_act] if g is not None and g.is_contiguous()])
             if any(g is not None and not g.is_contiguous() for g in res[:n_act]):
                 raise RuntimeError("hyperpri_amd: precision 'f16' cannot return a channels-last input gradient (whole networks only)")
         tape.sunk.clear()

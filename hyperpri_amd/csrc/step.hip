@@ -337,6 +337,127 @@ extern "C" int hpri_scale_tensors(float* const* tensors, const long long* numel,
   });
 }
 
+// ------------------------------------------------------------------------------------------------
+// Half-precision mode: the loss scale picked on the device from the gradient that enters the head
+//   s = min(static, 2^floor(log2(2 / max|gy|)))   (s = static when max|gy| is 0 or not finite)
+// slot[0] = s, slot[1] = 1 / s, slot[2 ..] the per-block maxima (HPRI_LOSS_SCALE_SLOT floats in all).
+// max is exact and order-free; the block partials and the one-block finish keep the launch free of atomics.
+// ------------------------------------------------------------------------------------------------
+#define LS_BLOCKS 256
+
+// |v|, with NaN counted as +inf: any non-finite element makes the maximum +inf
+__device__ __forceinline__ float ls_mag(float v) { return v == v ? fabsf(v) : __builtin_inff(); }
+
+__device__ __forceinline__ float ls_block_max(float m) {
+  __shared__ float red[STEP_THREADS];
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = STEP_THREADS / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(STEP_THREADS) void loss_scale_partial_kernel(const float* __restrict__ x, long long n,
+                                                                          float* __restrict__ part) {
+  float m = 0.f;
+  for (long long i = (long long)blockIdx.x * STEP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * STEP_THREADS)
+    m = fmaxf(m, ls_mag(x[i]));
+  m = ls_block_max(m);
+  if (threadIdx.x == 0) part[blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(STEP_THREADS) void loss_scale_finish_kernel(const float* __restrict__ part, int nblk, float stat,
+                                                                         float* __restrict__ slot) {
+  float m = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += STEP_THREADS) m = fmaxf(m, part[i]);
+  m = ls_block_max(m);
+  if (threadIdx.x == 0) {
+    float s = stat;
+    const float t = 2.f / m;                    // m = 0 or +inf: t = +inf or 0, s stays static
+    if (m > 0.f && t > 0.f && t < __builtin_inff()) {
+      int e;
+      frexpf(t, &e);                            // t = f * 2^e, f in [0.5, 1): floor(log2 t) = e - 1
+      const float p = ldexpf(1.f, e - 1 < -126 ? -126 : e - 1);     // (a normal number: 1 / s stays finite)
+      s = fminf(s, p);
+    }
+    slot[0] = s;
+    slot[1] = 1.f / s;
+  }
+}
+
+extern "C" int hpri_loss_scale_slot_floats(void) { return 2 + LS_BLOCKS; }
+
+extern "C" int hpri_loss_scale_pick(const float* gy, long long n, float stat, float* slot, hipStream_t stream) {
+  HPRI_REQUIRE(gy && slot && n > 0, "loss_scale_pick: bad arguments");
+  HPRI_REQUIRE(stat > 0.f, "loss_scale_pick: the static scale must be positive");
+  const long long want = (n + STEP_THREADS * 16 - 1) / (STEP_THREADS * 16);
+  const int nblk = (int)(want < LS_BLOCKS ? want : LS_BLOCKS);
+  hipLaunchKernelGGL(loss_scale_partial_kernel, dim3(nblk), dim3(STEP_THREADS), 0, stream, gy, n, slot + 2);
+  HPRI_CHECK_LAUNCH();
+  hipLaunchKernelGGL(loss_scale_finish_kernel, dim3(1), dim3(STEP_THREADS), 0, stream, slot + 2, nblk, stat, slot);
+  HPRI_CHECK_LAUNCH();
+  return HPRI_OK;
+}
+
+__global__ __launch_bounds__(STEP_THREADS) void scale_dev_kernel(OptTensors t, const float* __restrict__ slot, int invert) {
+  int k = 0;
+  while (k < t.count - 1 && (int)blockIdx.x >= t.blk_end[k]) ++k;
+  const int b0 = k ? t.blk_end[k - 1] : 0;
+  const long long base = (long long)(blockIdx.x - b0) * OPT_ELEMS_PER_BLOCK;
+  float* __restrict__ p = t.p[k];
+  const long long n = t.n[k];
+  const float scale = slot[invert ? 1 : 0];
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const long long i = base + j * STEP_THREADS + threadIdx.x;
+    if (i < n) p[i] *= scale;
+  }
+}
+
+// tensors[k][0 .. numel[k]) *= slot[0] (invert: slot[1] = 1 / slot[0]) -- hpri_scale_tensors with the factor on the device
+extern "C" int hpri_scale_tensors_dev(float* const* tensors, const long long* numel, int ntensors, const float* slot, int invert,
+                                      hipStream_t stream) {
+  HPRI_REQUIRE(tensors && numel && ntensors > 0 && slot, "scale_tensors_dev: bad arguments");
+  for (int k = 0; k < ntensors; ++k) HPRI_REQUIRE(numel[k] >= 0 && (numel[k] == 0 || tensors[k]), "scale_tensors_dev: null tensor pointer");
+  return opt_for_chunks(tensors, reinterpret_cast<const float* const*>(tensors), nullptr, nullptr, numel, ntensors,
+                        [&](const OptTensors& t, int blocks) {
+    hipLaunchKernelGGL(scale_dev_kernel, dim3(blocks), dim3(STEP_THREADS), 0, stream, t, slot, invert);
+    HPRI_CHECK_LAUNCH();
+    return HPRI_OK;
+  });
+}
+
+__global__ __launch_bounds__(STEP_THREADS) void unscale_acc_kernel(OptTensors t, const float* __restrict__ slot) {
+  int k = 0;
+  while (k < t.count - 1 && (int)blockIdx.x >= t.blk_end[k]) ++k;
+  const int b0 = k ? t.blk_end[k - 1] : 0;
+  const long long base = (long long)(blockIdx.x - b0) * OPT_ELEMS_PER_BLOCK;
+  float* __restrict__ d = t.p[k];
+  const float* __restrict__ s = t.g[k];
+  const long long n = t.n[k];
+  const float inv = slot[1];
+#pragma unroll 4
+  for (int j = 0; j < 16; ++j) {
+    const long long i = base + j * STEP_THREADS + threadIdx.x;
+    if (i < n) d[i] += s[i] * inv;          // (a power of two: the product is exact, one rounding in the sum)
+  }
+}
+
+// dst[k][i] += src[k][i] * slot[1], all tensors in one launch per 48: a loss-scaled gradient added, unscaled, to an accumulated one
+extern "C" int hpri_unscale_accumulate(float* const* dst, const float* const* src, const long long* numel, int ntensors,
+                                       const float* slot, hipStream_t stream) {
+  HPRI_REQUIRE(dst && src && numel && ntensors > 0 && slot, "unscale_accumulate: bad arguments");
+  for (int k = 0; k < ntensors; ++k)
+    HPRI_REQUIRE(numel[k] >= 0 && (numel[k] == 0 || (dst[k] && src[k])), "unscale_accumulate: null tensor pointer");
+  return opt_for_chunks(dst, src, nullptr, nullptr, numel, ntensors, [&](const OptTensors& t, int blocks) {
+    hipLaunchKernelGGL(unscale_acc_kernel, dim3(blocks), dim3(STEP_THREADS), 0, stream, t, slot);
+    HPRI_CHECK_LAUNCH();
+    return HPRI_OK;
+  });
+}
+
 extern "C" int hpri_sgd_step(float* const* params, const float* const* grads, float* const* momentum_buf,
                              const long long* numel, int ntensors, float lr, float momentum, float weight_decay,
                              int first_step, const float* grad_scale, hipStream_t stream) {

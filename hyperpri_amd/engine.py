@@ -38,6 +38,73 @@ LOWP = ("bf16", "bf16x3", "bf16x6")
 _SPLIT = {"bf16": 0, "bf16x3": 1, "bf16x6": 2}
 DEFAULT_PRECISION = os.environ.get("HPRI_PRECISION", "fp32")
 
+# precision "torch" (set_precision, or HPRI_PRECISION=torch): the mode follows PyTorch's own settings, resolved ONCE per forward call
+# of the outermost hyperpri module (per_call_precision) and used by every engine call of that forward; the tape's backward runs on
+# what the forward recorded (kernels, library, loss scale), whatever the state by then.
+TORCH = "torch"
+_CALL = threading.local()           # .mode: the mode resolved for the forward call in progress on this thread (None: none)
+
+
+def resolve_torch_precision() -> str:
+    """The mode a "torch" module runs under the current state: autocast on device type "cuda" (float16 -> "f16", bfloat16 -> "bf16"),
+    else torch.get_float32_matmul_precision() ("highest" -> "fp32", "high" -> "bf16x3": bf16 hi + lo, what PyTorch defines "high" as,
+    "medium" -> "bf16")."""
+    if torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        if dt == torch.float16:
+            return "f16"
+        if dt == torch.bfloat16:
+            return "bf16"
+        raise RuntimeError(f"hyperpri_amd: precision 'torch' has no mode for autocast dtype {dt} (float16 or bfloat16)")
+    return {"highest": "fp32", "high": "bf16x3", "medium": "bf16"}[torch.get_float32_matmul_precision()]
+
+
+def mode_of(module) -> str:
+    """The mode ``module`` runs in the current call: its explicit one ("f16" included), or the call's resolved one under "torch"."""
+    prec = getattr(module, "hpri_precision", None) or DEFAULT_PRECISION
+    if prec != TORCH:
+        return "f16" if getattr(module, "hpri_h16", None) == "f16" else prec
+    mode = getattr(_CALL, "mode", None)
+    return mode if mode is not None else resolve_torch_precision()
+
+
+def precision_of(module) -> str:
+    """The engine's contraction mode for ``module`` (what its ``hpri_precision`` says for an explicit mode: "f16" runs the "bf16" plane
+    paths, the 16-bit TYPE is the library's)."""
+    if (getattr(module, "hpri_precision", None) or DEFAULT_PRECISION) != TORCH:
+        return getattr(module, "hpri_precision", None) or DEFAULT_PRECISION
+    mode = mode_of(module)
+    return "bf16" if mode == "f16" else mode
+
+
+def lib_kind_of(module) -> Optional[str]:
+    """The library ``module``'s tapes launch into: "f16" (the half-precision build) or None."""
+    if (getattr(module, "hpri_precision", None) or DEFAULT_PRECISION) != TORCH:
+        return getattr(module, "hpri_h16", None)
+    return "f16" if mode_of(module) == "f16" else None
+
+
+def per_call_precision(forward):
+    """Decorator of the modules' ``forward``: the outermost "torch" module resolves the mode for the whole call."""
+    import functools
+
+    @functools.wraps(forward)
+    def wrapped(self, *args, **kw):
+        if getattr(_CALL, "mode", None) is not None or (getattr(self, "hpri_precision", None) or DEFAULT_PRECISION) != TORCH:
+            return forward(self, *args, **kw)
+        _CALL.mode = resolve_torch_precision()
+        try:
+            return forward(self, *args, **kw)
+        finally:
+            _CALL.mode = None
+    return wrapped
+
+
+# f16 mode, non-fused heads: the loss scale.  "adaptive": s = min(static, 2^floor(log2(2 / max|gy|))) picked on the device from the
+# gradient arriving at the logits (hpri_loss_scale_pick); "static": 2^ceil(log2(#logits)) as chosen on the host, i.e. a mean-reduced
+# loss assumed.  For a mean-reduced loss both give the same s (DESIGN.md, "Mixed precision").
+F16_LOSS_SCALE = "adaptive"
+
 
 def _rup(x: int, m: int) -> int:
     return (x + m - 1) // m * m
@@ -84,6 +151,30 @@ def scale_tensors_(tensors: List[torch.Tensor], scale: float) -> None:
     ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
     n = (ctypes.c_longlong * len(ts))(*[t.numel() for t in ts])
     _lib.call("hpri_scale_tensors", ptrs, n, len(ts), float(scale), _stream())
+
+
+def scale_tensors_dev_(tensors: List[torch.Tensor], slot: torch.Tensor, invert: bool) -> None:
+    """t *= slot[0] (``invert``: slot[1] = 1 / slot[0]) for every contiguous fp32 tensor of the list (hpri_scale_tensors_dev)."""
+    ts = [t for t in tensors if t is not None and t.numel() > 0]
+    if not ts:
+        return
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("hyperpri_amd: internal error: scale_tensors_dev_ wants contiguous fp32 tensors")
+    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    n = (ctypes.c_longlong * len(ts))(*[t.numel() for t in ts])
+    _lib.call("hpri_scale_tensors_dev", ptrs, n, len(ts), _p(slot), int(invert), _stream())
+
+
+def unscale_accumulate_(pairs: List[Tuple[torch.Tensor, torch.Tensor]], slot: torch.Tensor) -> None:
+    """dst += src * slot[1] for every (dst, src) pair of contiguous fp32 tensors (hpri_unscale_accumulate)."""
+    pairs = [(d, s) for d, s in pairs if d.numel() > 0]
+    if not pairs:
+        return
+    dst = (ctypes.c_void_p * len(pairs))(*[d.data_ptr() for d, _ in pairs])
+    src = (ctypes.c_void_p * len(pairs))(*[s.data_ptr() for _, s in pairs])
+    n = (ctypes.c_longlong * len(pairs))(*[d.numel() for d, _ in pairs])
+    _lib.call("hpri_unscale_accumulate", dst, src, n, len(pairs), _p(slot), _stream())
 
 
 def _p(t: Optional[torch.Tensor]) -> ctypes.c_void_p:
@@ -337,7 +428,7 @@ INPUT_RAW_OK = -3
 def input_planes_for(module, raw_ok: bool = False) -> int:
     """Planes the input layout pass should write for a network whose first layer is a 3x3 convolution (``raw_ok``: that layer is the
     program's first operation, a ``conv_bn_relu`` with one reader: see INPUT_RAW_OK)."""
-    prec = getattr(module, "hpri_precision", None) or DEFAULT_PRECISION
+    prec = precision_of(module)
     if not (PLANE_CONV and PLANE_PRODUCERS and prec == "bf16"):
         return 0
     if not (PLANES_ONLY_ACT and PLANE_WGRAD):
@@ -413,7 +504,10 @@ class Tape:
         self.delivered: set = set()                 # segmented tape: parameters whose gradient has left with an earlier slice
         self.done_to: Optional[int] = None          # segmented tape: the backward has run down to this node index (a slice's node runs one stage ahead)
         self.gscale = 1.0                           # half-precision mode: the power of two the head multiplies into the gradient (out_conv)
+        self.gslot: Optional[torch.Tensor] = None   # ... or, picked on the device (F16_LOSS_SCALE "adaptive"), [s, 1/s, ...] (hpri_loss_scale_pick)
         self._unscale: List[torch.Tensor] = []      # ... and the sunk gradients that still carry it (unscaled where their bucket is handed over)
+        self._acc_into: Dict[int, torch.Tensor] = {}     # id(parameter) -> bucket view its loss-scaled scratch gradient is added to (no_sync)
+        self._unscale_acc: List[Tuple[torch.Tensor, torch.Tensor]] = []     # (bucket view, scratch) pairs waiting for that addition
 
     def note_params(self, *params: Optional[torch.Tensor]) -> None:
         """Called by an op while it records its backward node: it will contribute to these parameters' gradients.  A
@@ -461,17 +555,51 @@ class Tape:
             got = sink.slot(p)             # (view of a flat all-reduce bucket, accumulate?) or None
             if got is not None:
                 g, acc = got
-                self.param_grads[id(p)] = g
                 self.sunk[id(p)] = p
+                if acc and self.gscale != 1.0:
+                    # half-precision mode, a later micro-batch: the bucket holds the unscaled sum so far, this gradient carries this
+                    # tape's loss scale -- it is written to scratch and added, unscaled, at the hand-over (_flush_unscale)
+                    self._acc_into[id(p)] = g
+                    g = self.param_grads[id(p)] = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+                    return g, 0
+                self.param_grads[id(p)] = g
                 return g, int(acc)
         g = torch.empty(p.shape, dtype=torch.float32, device=p.device)
         self.param_grads[id(p)] = g
         return g, 0
 
+    def unscale_(self, tensors: List[torch.Tensor]) -> None:
+        """Take this tape's loss scale out of (contiguous fp32) gradients in place."""
+        if self.gslot is not None:
+            scale_tensors_dev_(tensors, self.gslot, invert=True)
+        else:
+            scale_tensors_(tensors, 1.0 / self.gscale)
+
+    def _queue_unscale(self, pid: int) -> None:
+        """A sunk gradient is final: its loss scale leaves it at the hand-over of its bucket."""
+        dst = self._acc_into.pop(pid, None)
+        if dst is None:
+            self._unscale.append(self.param_grads[pid])
+        else:
+            self._unscale_acc.append((dst, self.param_grads[pid]))
+
     def _flush_unscale(self) -> None:
+        # (this may run on the hand-over stream: what it reads is marked as used there, so that it is not recycled before the read)
         if self._unscale:
-            scale_tensors_(self._unscale, 1.0 / self.gscale)
+            self.unscale_(self._unscale)
+            if self.gslot is not None:
+                self.gslot.record_stream(torch.cuda.current_stream(self.gslot.device))
             self._unscale.clear()
+        if self._unscale_acc:
+            slot = self.gslot
+            if slot is None:        # (the fused head's static scale)
+                slot = torch.tensor([self.gscale, 1.0 / self.gscale], dtype=torch.float32).to(self._unscale_acc[0][0].device)
+            unscale_accumulate_(self._unscale_acc, slot)
+            cur = torch.cuda.current_stream(slot.device)
+            for _, scratch in self._unscale_acc:
+                scratch.record_stream(cur)
+            slot.record_stream(cur)
+            self._unscale_acc.clear()
 
     def backward(self, lo: int = 0, hi: Optional[int] = None) -> None:
         """Run the recorded nodes ``[lo, hi)`` in reverse.  The whole tape by default; a segmented network (autograd.run_segmented:
@@ -496,7 +624,7 @@ class Tape:
                 # half-precision mode: the loss scale leaves the gradient before its bucket does.  The gradient may still be in flight
                 # on the second stream, so the unscale runs where the hand-over runs: on the stream that has waited for both.
                 if self.gscale != 1.0:
-                    self._unscale.append(self.param_grads[pid])
+                    self._queue_unscale(pid)
                 if self.used_side and getattr(sink, "completes_bucket", lambda q: True)(p):
                     # neither compute stream is held up: a third stream waits for both and hands the bucket over
                     dev = p.device
@@ -520,7 +648,7 @@ class Tape:
                 p = self.sunk.get(pid)
                 if p is not None and left > 0 and pid in self.param_grads:
                     if self.gscale != 1.0:
-                        self._unscale.append(self.param_grads[pid])
+                        self._queue_unscale(pid)
                     if self.used_side:
                         dev = p.device
                         iss = _issue_stream(dev)
@@ -532,8 +660,8 @@ class Tape:
                     else:
                         self._flush_unscale()
                         sink.ready(p)
-        if self._unscale:                           # (a bucket that never completes: finish() zeroes what did not land, the rest is unscaled here)
-            dev = self._unscale[0].device
+        if self._unscale or self._unscale_acc:      # (a bucket that never completes: finish() zeroes what did not land, the rest is unscaled here)
+            dev = (self._unscale or [self._unscale_acc[0][0]])[0].device
             iss = _issue_stream(dev)
             iss.wait_stream(torch.cuda.current_stream(dev))
             iss.wait_stream(_side(dev))
@@ -547,6 +675,7 @@ class Tape:
         self.bnpart.clear()
         self.gupl.clear()
         self.delivered.clear()
+        self._acc_into.clear()
 
 
 _IDENTITY_BN: Dict[tuple, "BNRef"] = {}
@@ -2047,7 +2176,7 @@ def concat_channels(tape: Tape, a: Act, b: Act) -> Act:
 def plane_gemm_mode(module, bnorm: bool = True) -> bool:
     """SpectralUNET in the bf16 mode with every switch of the plane path on: its skips are concatenated on planes (the two
     halves' producers write into one padded plane buffer) and the inner tensors exist as planes only."""
-    prec = getattr(module, "hpri_precision", None) or DEFAULT_PRECISION
+    prec = precision_of(module)
     return bool(bnorm and prec == "bf16" and PLANE_GEMM and PLANE_WGRAD and PLANE_PRODUCERS and PLANES_ONLY_ACT and PLANES_CAT1)
 
 
@@ -2061,7 +2190,7 @@ GRAD_BF16_INNER = FUSIONS
 
 
 def convt_planes_mode(module) -> bool:
-    prec = getattr(module, "hpri_precision", None) or DEFAULT_PRECISION
+    prec = precision_of(module)
     return bool(prec == "bf16" and CONVT_PLANES and PLANE_CONV and PLANE_WGRAD and PLANE_PRODUCERS and PLANES_CONVT and PLANES_CONCAT)
 
 
@@ -2179,7 +2308,8 @@ def out_conv(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.Tens
     if tape.record and _lib.kind() == "f16":
         # half-precision mode: activation gradients are stored as IEEE half (5 exponent bits).  The gradient of a MEAN-reduced loss
         # w.r.t. a logit is at most 1 / (number of logits): the head multiplies what arrives by the next power of two above that
-        # number, and the parameter gradients lose the factor again when they leave the tape (autograd._HipFn._backward)
+        # number, and the parameter gradients lose the factor again when they leave the tape (autograd._HipFn._backward).  The
+        # non-fused head lowers it on the device when what arrives is larger (F16_LOSS_SCALE, backward below).
         tape.gscale = float(2 ** max(0, (y.numel() - 1).bit_length()))
     slot = getattr(_PENDING, "bce", None)
     if fuse_loss and slot is not None and not slot.used and tape.record and slot.target.numel() == y.numel() and slot.target.device == dev:
@@ -2227,7 +2357,13 @@ def out_conv(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.Tens
                     _lib.call("hpri_set_loss_scale", tp.gscale)       # (the fused heads multiply it into the gradient they form)
                 else:
                     gy = gy.clone()                                   # (autograd's tensor is not ours to scale in place)
-                    scale_tensors_([gy], tp.gscale)
+                    if F16_LOSS_SCALE == "adaptive":
+                        # s = min(static, 2^floor(log2(2 / max|gy|))): a GradScaler-scaled or sum-reduced loss fits in half too
+                        tp.gslot = torch.empty(_lib.current().hpri_loss_scale_slot_floats(), dtype=torch.float32, device=dev)
+                        _lib.call("hpri_loss_scale_pick", _p(gy), gy.numel(), tp.gscale, _p(tp.gslot), _stream())
+                        scale_tensors_dev_([gy], tp.gslot, invert=False)
+                    else:
+                        scale_tensors_([gy], tp.gscale)
             dw, acc_w = tp.param_slot(weight)
             db = None
             if bias is not None:

@@ -66,9 +66,13 @@ def set_precision(module, precision):
     "bf16" / "f16" (16-bit MFMA operands and 16-bit stored activations: bf16, or IEEE half -- 11 mantissa bits instead of 8, the
     kernels of libhyperpri_hip_f16.so, activation gradients under a power-of-two loss scale chosen from the number of logits of a
     mean-reduced loss), "bf16x3" / "bf16x6" (fp32 operands split into 2 / 3 bf16 planes).  Not part of the reference API.
-    "f16" is a mode of whole networks (UNet / CubeNET / SpectralUNET): the loss scale enters at their output layer."""
-    if precision not in E.PRECISIONS + ("f16",):
-        raise ValueError(f"precision must be one of {E.PRECISIONS + ('f16',)}")
+    "f16" is a mode of whole networks (UNet / CubeNET / SpectralUNET): the loss scale enters at their output layer.
+    "torch": the mode follows PyTorch's own settings, resolved once per forward call -- torch.autocast("cuda", float16 / bfloat16) ->
+    "f16" / "bf16", else torch.set_float32_matmul_precision "highest" / "high" / "medium" -> "fp32" / "bf16x3" / "bf16"; a call then
+    runs exactly what the module set to that mode runs (engine.resolve_torch_precision)."""
+    choices = E.PRECISIONS + ("f16", E.TORCH)
+    if precision not in choices:
+        raise ValueError(f"precision must be one of {choices}")
     for m in module.modules():
         m.hpri_precision = "bf16" if precision == "f16" else precision      # (the engine's plane paths; the 16-bit TYPE is the library's)
         m.hpri_h16 = "f16" if precision == "f16" else None
@@ -87,7 +91,7 @@ class DoubleConv(nn.Module):
         self.double_conv = nn.Sequential(*layers)
 
     def _gen(self, tape, x, need_dx=True, room=0, out_planes=False, head_next=False):
-        return _double_conv_gen(tape, x, self.double_conv, self.training, need_dx, getattr(self, "hpri_precision", None), room,
+        return _double_conv_gen(tape, x, self.double_conv, self.training, need_dx, E.precision_of(self), room,
                                 out_planes, head_next)
 
     def _ops(self, *args, **kw):
@@ -98,9 +102,10 @@ class DoubleConv(nn.Module):
         seq = self.double_conv
         return [[seq[0], seq[1]], [seq[3], seq[4]]]
 
+    @E.per_call_precision
     def forward(self, x):
         return run(lambda tape, a, need: self._ops(tape, a[0], need[0]), [x], list(self.parameters()), name="double_conv",
-                   lib_kind=getattr(self, "hpri_h16", None))
+                   lib_kind=E.lib_kind_of(self))
 
 
 class Down(nn.Module):
@@ -119,8 +124,9 @@ class Down(nn.Module):
     def _stages(self):
         return self.maxpool_conv[1]._stages()
 
+    @E.per_call_precision
     def forward(self, x):
-        return run(lambda tape, a, need: self._ops(tape, a[0]), [x], list(self.parameters()), name="down", lib_kind=getattr(self, "hpri_h16", None))
+        return run(lambda tape, a, need: self._ops(tape, a[0]), [x], list(self.parameters()), name="down", lib_kind=E.lib_kind_of(self))
 
 
 class Up(nn.Module):
@@ -147,7 +153,7 @@ class Up(nn.Module):
         b = None if self.bilinear else self.up.bias
         join = E.up_attention if self.use_attention else E.up_concat
         return self.conv._gen(tape, join(tape, x1, x2, w, b, need_dx1=need_dx1,
-                                         precision=getattr(self, "hpri_precision", None)), out_planes=out_planes, head_next=head_next)
+                                         precision=E.precision_of(self)), out_planes=out_planes, head_next=head_next)
 
     def _ops(self, *args, **kw):
         return _drain(self._gen(*args, **kw))
@@ -156,9 +162,10 @@ class Up(nn.Module):
         first, second = self.conv._stages()
         return [[self.up] + first, second]            # (nn.Upsample has no parameters)
 
+    @E.per_call_precision
     def forward(self, x1, x2):
         return run(lambda tape, a, need: self._ops(tape, a[0], a[1], need[0]), [x1, x2], list(self.parameters()), name="up",
-                   lib_kind=getattr(self, "hpri_h16", None))
+                   lib_kind=E.lib_kind_of(self))
 
 
 class OutConv(nn.Module):
@@ -171,6 +178,7 @@ class OutConv(nn.Module):
     def _ops(self, tape, x, need_dx=True):
         return E.out_conv(tape, x, self.conv.weight, self.conv.bias, need_dx)
 
+    @E.per_call_precision
     def forward(self, x):
         return run(lambda tape, a, need: self._ops(tape, a[0], need[0]), [x], list(self.parameters()), name="out_conv",
-                   lib_kind=getattr(self, "hpri_h16", None))
+                   lib_kind=E.lib_kind_of(self))

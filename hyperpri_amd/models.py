@@ -74,6 +74,7 @@ class UNet(nn.Module):
         st[-1] = st[-1] + [self.outc]
         return st
 
+    @E.per_call_precision
     def forward(self, x):
         E.throttle(x.device)
         if self.fused_tape and not has_hooks(self):
@@ -100,7 +101,7 @@ class UNet(nn.Module):
                 y = yield from self.up4._gen(tape, y, x1, head_next=True)          # (bf16 mode: the head reads its input as bf16 planes)
                 return self.outc._ops(tape, y)
             logits = run_staged(prog, [x], _stage_params(self), self.fused_tape, input_planes=E.input_planes_for(self), name="unet",
-                                lib_kind=getattr(self, "hpri_h16", None))
+                                lib_kind=E.lib_kind_of(self))
         else:
             x1 = self.inc(x)
             x2 = self.down1(x1)
@@ -148,7 +149,7 @@ class SpectralUNET(torch.nn.Module):
     def _layer(self, tape, x, seq, need_dx=True, **kw):
         bn = E.BNRef(seq[1]) if self._bnorm else None
         return E.conv_bn_relu(tape, x, seq[0].weight, seq[0].bias, bn, self.training, 1, groups=x.N, need_dx=need_dx,
-                              precision=getattr(self, "hpri_precision", None), relu_without_bn=not self._bnorm, **kw)
+                              precision=E.precision_of(self), relu_without_bn=not self._bnorm, **kw)
 
     fused_tape = True       # see UNet.fused_tape (no per-child route here: the reference's forward is one loop over images)
 
@@ -156,12 +157,13 @@ class SpectralUNET(torch.nn.Module):
         return [[self.tail], [self.down1], [self.down2], [self.down3], [self.down4], [self.up1], [self.up2], [self.up3],
                 [self.up4, self.outc]]
 
+    @E.per_call_precision
     def forward(self, x):
         E.throttle(x.device)
         def prog(tape, a, need):
             L = self._layer
             if E.plane_gemm_mode(self, self._bnorm) and (tape.record or self.training or not E.FOLD_EVAL_BN
-                                                          or E.predict_gemm_planes_ok(getattr(self, "hpri_precision", None))):
+                                                          or E.predict_gemm_planes_ok(E.precision_of(self))):
                 # bf16 mode: the three inner skips are concatenated on bf16 planes -- the producers of both halves write into one
                 # padded plane buffer ([skip | zeros to a multiple of 32 | up]), the consumer's weight packs carry the gap -- and the
                 # tensors between the layers exist as planes only (torch.cat of models.py:139-143 without a byte moved)
@@ -211,7 +213,7 @@ class SpectralUNET(torch.nn.Module):
             yield
             t = L(tape, E.concat_channels(tape, x1, t), self.up4)
             return E.out_conv(tape, E.concat_channels(tape, x0, t), self.outc.weight, self.outc.bias, fuse_loss=self.n_classes == 1)
-        out = run_staged(prog, [x], _stage_params(self), self.fused_tape, name="spectral_unet", lib_kind=getattr(self, "hpri_h16", None))
+        out = run_staged(prog, [x], _stage_params(self), self.fused_tape, name="spectral_unet", lib_kind=E.lib_kind_of(self))
         if self.n_classes != 1:
             # models.py:144 stores each image's (R*C, n_classes) result with .reshape(n_classes, R, C): the FLAT order is
             # pixel-major, class-minor.  `out` holds true class planes (N, K, R, C); re-order to the reference's element order
@@ -254,7 +256,7 @@ class CubeNET(torch.nn.Module):
         self.outc = OutConv(64, self.n_classes)
 
     def _stem_gen(self, tape, x, need_dx, room=0):
-        prec = getattr(self, "hpri_precision", None)
+        prec = E.precision_of(self)
         h = E.conv_bn_relu(tape, x, self.first_conv.weight, self.first_conv.bias, E.BNRef(self.inc[1]),
                            self.training, 3, need_dx=need_dx, precision=prec, next_cout=self.inc2[0].weight.shape[0])
         yield
@@ -266,7 +268,7 @@ class CubeNET(torch.nn.Module):
 
     def _stem(self, x):
         params = list(self.inc.parameters()) + list(self.inc2.parameters())
-        return run(lambda tape, a, need: self._stem_ops(tape, a[0], need[0]), [x], params, name="cubenet_stem", lib_kind=getattr(self, "hpri_h16", None))
+        return run(lambda tape, a, need: self._stem_ops(tape, a[0], need[0]), [x], params, name="cubenet_stem", lib_kind=E.lib_kind_of(self))
 
     def _up4_gen(self, tape, y, x1, need_dx1=True, head_next=False):
         """Last decoder stage: ``up4`` (first_depth 64) or the inline upsample4 -> pad -> cat -> upconv4 (models.py:229-240)."""
@@ -274,7 +276,7 @@ class CubeNET(torch.nn.Module):
             return self.up4._gen(tape, y, x1, need_dx1, head_next=head_next)
         w4 = None if self.bilinear else self.upsample4.weight
         b4 = None if self.bilinear else self.upsample4.bias
-        cat = E.up_concat(tape, y, x1, w4, b4, need_dx1=need_dx1, precision=getattr(self, "hpri_precision", None))
+        cat = E.up_concat(tape, y, x1, w4, b4, need_dx1=need_dx1, precision=E.precision_of(self))
         return self.upconv4._gen(tape, cat, head_next=head_next)
 
     def _up4_ops(self, *args, **kw):
@@ -294,6 +296,7 @@ class CubeNET(torch.nn.Module):
         st[-1] = st[-1] + [self.outc]
         return st
 
+    @E.per_call_precision
     def forward(self, x):
         if x.dim() != 5 or x.shape[2] != self.depth:
             raise ValueError(f"CubeNET expects (N,1,{self.depth},R,C), got {tuple(x.shape)}")
@@ -321,7 +324,7 @@ class CubeNET(torch.nn.Module):
                 y = yield from self._up4_gen(tape, y, x1, head_next=True)
                 return self.outc._ops(tape, y)
             logits = run_staged(prog, [x], _stage_params(self), self.fused_tape, input_planes=E.input_planes_for(self, raw_ok=True), name="cubenet",
-                                lib_kind=getattr(self, "hpri_h16", None))
+                                lib_kind=E.lib_kind_of(self))
         else:
             x1 = self._stem(x)
             x2 = self.down1(x1)
@@ -336,7 +339,7 @@ class CubeNET(torch.nn.Module):
             else:
                 params4 = list(self.upsample4.parameters()) + list(self.upconv4.parameters())
                 y = run(lambda tape, a, need: self._up4_ops(tape, a[0], a[1], need[0]), [y, x1], params4, name="cubenet_up4",
-                        lib_kind=getattr(self, "hpri_h16", None))
+                        lib_kind=E.lib_kind_of(self))
             logits = self.outc(y)
         if self.analyze:
             return (logits, logits, torch.sigmoid(logits))

@@ -74,6 +74,17 @@ int hpri_item_queue_bytes(void);
  * eight exponent bits) both exist and the scale stays 1. */
 int hpri_set_loss_scale(float scale);
 int hpri_scale_tensors(float* const* tensors, const long long* numel, int ntensors, float scale, hipStream_t stream);
+/* The scale of the non-fused heads is picked on the device from the gradient that arrives at the logits (a GradScaler-scaled or
+ * sum-reduced loss brings one far above 1 / #logits): hpri_loss_scale_pick(gy, n, static, slot) writes
+ * s = min(static, 2^floor(log2(2 / max|gy[0..n)|))) -- static when that maximum is 0 or not finite -- to slot[0] and 1 / s to slot[1];
+ * slot is device memory of hpri_loss_scale_slot_floats() floats (the rest holds block maxima), no host synchronisation.
+ * hpri_scale_tensors_dev is hpri_scale_tensors with the factor read from slot[0] (invert != 0: slot[1]);
+ * hpri_unscale_accumulate: dst[k][i] += src[k][i] * slot[1] (a micro-batch's loss-scaled gradient added, unscaled, to the sum). */
+int hpri_loss_scale_slot_floats(void);
+int hpri_loss_scale_pick(const float* gy, long long n, float stat, float* slot, hipStream_t stream);
+int hpri_scale_tensors_dev(float* const* tensors, const long long* numel, int ntensors, const float* slot, int invert, hipStream_t stream);
+int hpri_unscale_accumulate(float* const* dst, const float* const* src, const long long* numel, int ntensors, const float* slot,
+                            hipStream_t stream);
 int hpri_set_item_queue(void* queue, size_t bytes, hipStream_t stream);
 
 /* ---- weight packing: nn.Parameter layouts -> [chunk][tap][32][Ncols_pad] LDS panels ---------------
