@@ -494,6 +494,26 @@ int hpri_hwb_ingest(const void* src, int src_dtype, float* dst, long long P, int
                     int dst_cw, hipStream_t stream);
 int hpri_hwb_h2d(const float* host_src, float* dst, long long P, int B, int lo, int C, int dst_cs, hipStream_t stream);
 
+/* ---- device-resident cube cache (cache.hip; hyperpri_amd/cache.py) ----------------------------------------
+ * A training split is stored once in device memory and every batch is assembled from it by one gather pass that crops
+ * and flips on the way (the reference's augmentation: RandomCrop with one RNG state for image and mask,
+ * params_HyperPRI.py:201-203, dataset.py:283-293).  dtype arguments: 0 = float32, 1 = float16.
+ *   hpri_hwb_store    device (P, B) f32/f16 pixel-major cube -> one cache slot (P, cs), cs = roundup(C, 8) (cs % 8 == 0 is
+ *                     required): bands [lo, lo+C) at channels [0, C), zeros at [C, cs); the slot is f32 or f16.
+ *   hpri_cube_gather  cache (slots, Hs, Ws, cs) f32/f16 -> dst (N, h, w, cs) fp32, zero-padded channels-last:
+ *                       dst[i, y, x, :] = cache[slot_i, top_i + (flags_i & 1 ? h-1-y : y), left_i + (flags_i & 2 ? w-1-x : x), :]
+ *                     table: N entries {slot, top, left, flags} of four int32 in DEVICE memory, 16-byte aligned.
+ *   hpri_mask_gather  the same table, crop and flips over uint8 masks (slots, Hs, Ws) -> fp32 (N, 1, h, w).
+ * A window larger than the frame (h > Hs or w > Ws) is an argument error.  The launchers cannot read the table: the kernels
+ * clamp slot, top and left into the cache, so a bad entry yields the wrong window but never an access outside the buffers;
+ * callers validate their tables on the host. */
+int hpri_hwb_store(const void* src, int src_dtype, void* dst, int dst_dtype, long long P, int B, int lo, int C, int cs,
+                   hipStream_t stream);
+int hpri_cube_gather(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const int* table, int N, int h,
+                     int w, float* dst, hipStream_t stream);
+int hpri_mask_gather(const unsigned char* masks, int slots, int Hs, int Ws, const int* table, int N, int h, int w,
+                     float* dst, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
