@@ -824,6 +824,18 @@ extern "C" int hpri_col_sum(const float* src, int cs, int coff, float* out, int 
   return HPRI_OK;
 }
 
+// The second stage of every two-stage column reduction on its own: sums[k][c] = sum over `nblk` partial rows [nblk][2][Cpart]
+// (double accumulation, fixed order), out1 / out2 (optional) (+)= the two sums, zero_out (optional) cleared.  For sweeps that live
+// in another file and leave partial rows of this layout (elementwise.hip: the fused head and pooling backward sweeps).
+extern "C" int hpri_col_finalize(const float* part, int nblk, int Cpart, int C, float* sums, float* out1, float* out2,
+                                 int accumulate, float* zero_out, hipStream_t stream) {
+  HPRI_REQUIRE(part && sums && nblk > 0 && C > 0 && Cpart >= C, "col_finalize: bad arguments");
+  hipLaunchKernelGGL(col_finalize_kernel, dim3(hpri_cdiv(C, 32), 1), dim3(1024), 0, stream, part, nblk, Cpart, C, sums, out1, out2,
+                     accumulate, zero_out);
+  HPRI_CHECK_LAUNCH();
+  return HPRI_OK;
+}
+
 // ---- column sums from per-tile statistics records --------------------------------------------------------------------
 // out[c] (+)= sum over tiles of mean * count of channel c0 + c, from the (mean, M2, count, 0) records a convolution epilogue
 // leaves (hpri_conv_wino4 / hpri_conv_bf16v3 / hpri_conv_fwd with `stats`).  Used for the bias gradient of a

@@ -388,6 +388,92 @@ __global__ __launch_bounds__(256) void outconv_fwd_kernel(const float* __restric
   }
 }
 
+// The last stage's BatchNorm (+ ReLU) and the one-class head in ONE sweep of the pre-BN tensor x: y = relu(x * scale + shift) by
+// bn_apply_relu_kernel's expression (pad channels selected as zeros) is formed in registers and never stored; the dot product with
+// the weight row, the bias, the store and the loss element are those of outconv_fwd_kernel's one-class path (lane gl adds the quads
+// gl, gl + 16, ... in that order, butterfly, four pixels in flight per 16-lane group; outconv_fwd_wide_kernel forms the same sums
+// for C % 4 != 0), so logits and loss partials are bit for bit those of hpri_bn_apply_relu + hpri_outconv_fwd(_bce).  C <= 256.
+// s + a * b with the product rounded on its own (no contraction into a fused multiply-add)
+__device__ __forceinline__ float oc_mul_then_add(float a, float b, float s) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return s + p;
+}
+
+template <bool BCE, int NJ>      // NJ = channel quads per lane = ceil(C / 64): the registers of the unused quads cost occupancy
+__global__ __launch_bounds__(256) void bn_outconv_fwd_kernel(const float* __restrict__ x, int x_cs, int x_coff, const float* __restrict__ scale,
+                                                             const float* __restrict__ shift, int relu, const float* __restrict__ w,
+                                                             const float* __restrict__ b, float* __restrict__ y, long long NP, int C,
+                                                             const float* __restrict__ target, double* __restrict__ partial) {
+  __shared__ double bred[256];
+  double bsum = 0.0;
+  const int gl = threadIdx.x & 15;
+  const long long grp = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+  const long long ngrp = ((long long)gridDim.x * blockDim.x) >> 4;
+  const int C4 = (C + 3) >> 2;
+  float wq[NJ][4], sq[NJ][4], hq[NJ][4];
+  int qi[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const int q = gl + 16 * j;
+    qi[j] = min(q, C4 - 1) * 4;                                      // (lanes beyond the channels read a valid quad and weigh it by zero)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool ok = qi[j] + k < C;
+      wq[j][k] = (q < C4 && ok) ? w[qi[j] + k] : 0.f;
+      sq[j][k] = ok ? scale[qi[j] + k] : 0.f;
+      hq[j][k] = ok ? shift[qi[j] + k] : 0.f;
+    }
+  }
+  const float b0 = b ? b[0] : 0.f;
+  const bool fused = (C & 3) != 0;
+  for (long long pg0 = grp; pg0 < NP; pg0 += 4 * ngrp) {
+    float4 v[4][NJ];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long pg = min(pg0 + u * ngrp, NP - 1);
+      const float* xp = x + pg * x_cs + x_coff;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) v[u][j] = *reinterpret_cast<const float4*>(xp + qi[j]);
+    }
+    float mine = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+          const float xx[4] = {v[u][j].x, v[u][j].y, v[u][j].z, v[u][j].w};
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            float o = (qi[j] + k < C) ? xx[k] * sq[j][k] + hq[j][k] : 0.f;
+            if (relu) o = fmaxf(o, 0.f);
+            // the two kernels this one replaces round differently as compiled: outconv_fwd_kernel's one-class path (C % 4 == 0)
+            // rounds each product before it is added (packed multiplies), outconv_fwd_wide_kernel (C % 4 != 0) fuses product and
+            // sum -- stated here explicitly so that the logits stay theirs (tests/test_gpu_bn_fused_sweeps.py compares bit for bit)
+            s = fused ? __fmaf_rn(o, wq[j][k], s) : oc_mul_then_add(o, wq[j][k], s);
+          }
+        }
+      s += __shfl_xor(s, 8, 16); s += __shfl_xor(s, 4, 16); s += __shfl_xor(s, 2, 16); s += __shfl_xor(s, 1, 16);
+      if (gl == u) mine = s;
+    }
+    const long long pgm = pg0 + gl * ngrp;
+    if (gl < 4 && pgm < NP) {
+      const float o = mine + b0;
+      y[pgm] = o;
+      if (BCE) bsum += (double)oc_bce_elem(o, target[pgm]);
+    }
+  }
+  if (BCE) {
+    bred[threadIdx.x] = bsum;
+    __syncthreads();
+    for (int wd = 128; wd > 0; wd >>= 1) {
+      if (threadIdx.x < wd) bred[threadIdx.x] += bred[threadIdx.x + wd];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = bred[0];
+  }
+}
+
 // One class over MANY channels (SpectralUNET's Linear(2F, 1), models.py:103: 3300 channels) or over bf16 rows: the weight row sits
 // in LDS (zero beyond C), a 16-lane group walks its pixel in 16-byte pieces per lane (4 fp32 / 8 bf16 channels) with four pixels in
 // flight.  fp32 sources: lane gl adds the quads gl, gl + 16, ... in that order, then the butterfly -- the sums of the kernel above.
@@ -630,6 +716,376 @@ __global__ void outconv_bwd_weight_finalize_kernel(const float* __restrict__ par
   if (threadIdx.x == 0) {
     if (c < C) { float* o = dw + (size_t)k * C + c; *o = accumulate ? *o + (float)red[0] : (float)red[0]; }
     else if (db != nullptr) db[k] = accumulate ? db[k] + (float)red[0] : (float)red[0];
+  }
+}
+
+// ---------------------------------- sweeps fused with the BatchNorm backward --------------------
+// The last stage of a U-Net is conv -> BN -> ReLU -> y -> 1x1 head (one class).  The gradient the head hands to y is the rank-1
+// tensor g[p][c] = dlogit[p] * w[c]: writing it (outconv_bwd_data_kernel), reading y for the head's weight gradient
+// (outconv_bwd_weight_kernel) and reading g twice more in the BatchNorm backward (bn.hip: col_reduce, bn_bwd_apply) moved 2.1 GB per
+// step at 608 x 968 x 2 x 64 channels.  The two kernels below form g in registers and recompute y from the pre-BN tensor x, which
+// the BatchNorm backward reads anyway: 0.9 GB.
+//
+// stage 1: one sweep of x and the logit-gradient source; per block the partial rows of BOTH reductions it replaces, in their
+// layouts and with their per-thread summation order (thread map of col_reduce_kernel / outconv_bwd_weight_kernel: grid = (pixel
+// blocks, channel-quad blocks), block = rows x CQ, ascending pixels), so the sums are bit for bit today's:
+//   bnpart[blk][2][Cpart]: sum g * [y > 0], sum g * [y > 0] * xhat         (col_finalize_kernel)
+//   hwpart[blk][2][Cpart]: row 0 = sum dlogit * y, row 1 element 0 = sum dlogit   (outconv_bwd_weight_finalize_kernel, K = 1)
+// BCE: `dy` holds the logits and dlogit = (sigmoid(logit) - target) * gs is formed once per pixel and shared by its lane group.
+template <bool BCE>
+__global__ __launch_bounds__(256) void bn_head_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ target,
+                                                             const float* __restrict__ gscale, float lscale, const float* __restrict__ x,
+                                                             int x_cs, int x_coff, const float* __restrict__ w,
+                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             long long NP, int C, int CQ, int relu, float* __restrict__ bnpart,
+                                                             float* __restrict__ hwpart, int Cpart) {
+  const float gs = BCE ? (gscale ? gscale[0] : 1.f) / (float)((double)NP) * lscale : 1.f;
+  __shared__ float4 red[3][256];
+  __shared__ float redb[256];
+  const int rows = 256 / CQ;
+  const int cq = threadIdx.x % CQ, pr = threadIdx.x / CQ;
+  const int c = (blockIdx.y * CQ + cq) * 4;
+  const bool live = c < C;
+  const long long per = (NP + gridDim.x - 1) / gridDim.x;
+  const long long p0 = (long long)blockIdx.x * per;
+  const long long p1 = (p0 + per < NP) ? p0 + per : NP;
+  float mu[4], is[4], sc[4], sh[4], wv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool ok = c + j < C;
+    mu[j] = ok ? mean[c + j] : 0.f;
+    is[j] = ok ? invstd[c + j] : 0.f;
+    sc[j] = ok ? scale[c + j] : 0.f;
+    sh[j] = ok ? shift[c + j] : 0.f;
+    wv[j] = ok ? w[c + j] : 0.f;
+  }
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, sw[4] = {0.f, 0.f, 0.f, 0.f};
+  float sb = 0.f;
+  // one pixel's terms: y by bn_apply_relu_kernel's expression (pad channels selected as zeros), g = 0 + dlogit * w (the rounding of
+  // outconv_bwd_data_kernel), the mask and xhat of col_reduce_kernel
+  auto add = [&](float gl, const float4& xq) {
+    sb += gl;
+    if (!live) return;
+    const float xx[4] = {xq.x, xq.y, xq.z, xq.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float t = xx[j] * sc[j] + sh[j];
+      const float y = (c + j < C) ? (relu ? fmaxf(t, 0.f) : t) : 0.f;
+      sw[j] += gl * y;
+      const float gv = 0.f + gl * wv[j];
+      const float gj = (!relu || (t > 0.f)) ? gv : 0.f;
+      s1[j] += gj;
+      s2[j] += gj * ((xx[j] - mu[j]) * is[j]);
+    }
+  };
+  // UF pixels per thread and iteration, all loads issued before the first use; the summation order per thread does not depend on
+  // UF (pixels in ascending order).  Measured alone at 608 x 968 x 2 x 64: UF = 4 (104 registers, 4 waves per SIMD = the whole
+  // grid resident) 80 us = 3.9 TB/s; UF = 8 (160 registers, 3 waves per SIMD) 96 us = 3.3 TB/s.  The two reductions it replaces
+  // ran at 3.0 (outconv_bwd_weight_kernel) and 4.5 TB/s (col_reduce_kernel) with the same block plan, which bit-equal sums fix.
+  constexpr int UF = 4;
+  long long p = p0 + pr;
+  for (; p + (UF - 1) * rows < p1; p += UF * rows) {
+    float g[UF];
+    float4 xv[UF];
+#pragma unroll
+    for (int u = 0; u < UF; ++u) {
+      const long long pg = p + u * rows;
+      g[u] = dy[pg];
+      if (BCE && CQ < UF) g[u] = oc_bce_grad(g[u], target[pg]) * gs;
+      xv[u] = live ? *reinterpret_cast<const float4*>(x + pg * x_cs + x_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (BCE && CQ >= UF) {     // one exp + division per pixel: lane u of the group does pixel u (outconv_bwd_weight_kernel's exchange)
+      float lg = 0.f, lt = 0.f;
+#pragma unroll
+      for (int u = 0; u < UF; ++u)
+        if (cq == u) { lg = g[u]; lt = target[p + u * rows]; }
+      const float mine = oc_bce_grad(lg, lt) * gs;
+#pragma unroll
+      for (int u = 0; u < UF; ++u) g[u] = __shfl(mine, (threadIdx.x & 63 & ~(CQ - 1)) + u, 64);
+    }
+#pragma unroll
+    for (int u = 0; u < UF; ++u) add(g[u], xv[u]);
+  }
+  for (; p < p1; p += rows) {
+    float g = dy[p];
+    if (BCE) g = oc_bce_grad(g, target[p]) * gs;
+    const float4 xq = live ? *reinterpret_cast<const float4*>(x + p * x_cs + x_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    add(g, xq);
+  }
+  red[0][threadIdx.x] = make_float4(s1[0], s1[1], s1[2], s1[3]);
+  red[1][threadIdx.x] = make_float4(s2[0], s2[1], s2[2], s2[3]);
+  red[2][threadIdx.x] = make_float4(sw[0], sw[1], sw[2], sw[3]);
+  redb[threadIdx.x] = sb;
+  __syncthreads();
+  if (pr == 0) {
+    float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1, t3 = t1;
+    float tb = 0.f;
+    for (int r = 0; r < rows; ++r) {
+      const float4 a = red[0][r * CQ + cq], b = red[1][r * CQ + cq], d = red[2][r * CQ + cq];
+      t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
+      t2.x += b.x; t2.y += b.y; t2.z += b.z; t2.w += b.w;
+      t3.x += d.x; t3.y += d.y; t3.z += d.z; t3.w += d.w;
+      tb += redb[r * CQ + cq];
+    }
+    float* o = bnpart + ((size_t)blockIdx.x * 2) * Cpart + c;        // (c < Cpart: the grid has Cpart / 4 / CQ channel blocks)
+    *reinterpret_cast<float4*>(o) = t1;
+    *reinterpret_cast<float4*>(o + Cpart) = t2;
+    float* h = hwpart + ((size_t)blockIdx.x * 2) * Cpart;
+    *reinterpret_cast<float4*>(h + c) = t3;
+    if (blockIdx.y == 0 && cq == 0) h[Cpart] = tb;
+  }
+}
+
+// stage 2: dx = scale * (g - s1/Np - xhat * s2/Np) (bn_bwd_apply_kernel's arithmetic and thread map, four pixels in flight) with g
+// formed as in stage 1; reads x and the logit-gradient source only.  dxpart (optional): per-block column sums of dx.
+template <bool BCE>
+__global__ __launch_bounds__(256) void bn_head_apply_kernel(const float* __restrict__ dy, const float* __restrict__ target,
+                                                            const float* __restrict__ gscale, float lscale, const float* __restrict__ x,
+                                                            int x_cs, int x_coff, const float* __restrict__ w, float* __restrict__ dx,
+                                                            int dx_cs, int dx_coff, const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, const float* __restrict__ sums, int NP, int C,
+                                                            int Cw, int CQ, int relu, int use_batch_stats, float* __restrict__ dxpart,
+                                                            int Cpart) {
+  const float gs = BCE ? (gscale ? gscale[0] : 1.f) / (float)((double)NP) * lscale : 1.f;
+  __shared__ float4 red[256];
+  const int rows = 256 / CQ;
+  const int cq = threadIdx.x % CQ, pr = threadIdx.x / CQ;
+  const int c = (blockIdx.y * CQ + cq) * 4;
+  const bool live = c < Cw;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  const float inv_np = 1.f / (float)NP;
+  float sc[4], sh[4], mu[4], is[4], k1[4], k2[4], wv[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool ok = c + j < C;
+    sc[j] = ok ? scale[c + j] : 0.f;
+    sh[j] = ok ? shift[c + j] : 0.f;
+    mu[j] = ok ? mean[c + j] : 0.f;
+    is[j] = ok ? invstd[c + j] : 0.f;
+    wv[j] = ok ? w[c + j] : 0.f;
+    k1[j] = (ok && use_batch_stats) ? sums[c + j] * inv_np : 0.f;
+    k2[j] = (ok && use_batch_stats) ? sums[C + c + j] * inv_np : 0.f;
+  }
+  auto put = [&](long long q, float gl, const float4& xq) {
+    const float xx[4] = {xq.x, xq.y, xq.z, xq.w};
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gv = 0.f + gl * wv[j];
+      const float gj = (!relu || (xx[j] * sc[j] + sh[j] > 0.f)) ? gv : 0.f;
+      const float xh = (xx[j] - mu[j]) * is[j];
+      o[j] = (c + j < C) ? sc[j] * (gj - k1[j] - xh * k2[j]) : 0.f;   // pad channels stay exactly zero
+      acc[j] += o[j];
+    }
+    *reinterpret_cast<float4*>(dx + (size_t)q * dx_cs + dx_coff + c) = make_float4(o[0], o[1], o[2], o[3]);
+  };
+  const long long per = ((long long)NP + gridDim.x - 1) / gridDim.x;
+  const long long q0 = (long long)blockIdx.x * per;
+  const long long q1 = (q0 + per < NP) ? q0 + per : NP;
+  long long q = q0 + pr;
+  for (; q + 3 * rows < q1; q += 4 * rows) {
+    float g[4];
+    float4 xv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long pg = q + u * rows;
+      g[u] = dy[pg];
+      if (BCE && CQ < 4) g[u] = oc_bce_grad(g[u], target[pg]) * gs;
+      xv[u] = live ? *reinterpret_cast<const float4*>(x + (size_t)pg * x_cs + x_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (BCE && CQ >= 4) {
+      float lg = 0.f, lt = 0.f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (cq == u) { lg = g[u]; lt = target[q + u * rows]; }
+      const float mine = oc_bce_grad(lg, lt) * gs;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) g[u] = __shfl(mine, (threadIdx.x & 63 & ~(CQ - 1)) + u, 64);
+    }
+    if (live) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) put(q + u * rows, g[u], xv[u]);
+    }
+  }
+  if (live)
+    for (; q < q1; q += rows) {
+      float g = dy[q];
+      if (BCE) g = oc_bce_grad(g, target[q]) * gs;
+      put(q, g, *reinterpret_cast<const float4*>(x + (size_t)q * x_cs + x_coff + c));
+    }
+  if (dxpart != nullptr) {
+    red[threadIdx.x] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    __syncthreads();
+    if (pr == 0 && c < Cpart) {
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int r = 0; r < rows; ++r) { const float4 a = red[r * CQ + cq]; t.x += a.x; t.y += a.y; t.z += a.z; t.w += a.w; }
+      float* o = dxpart + ((size_t)blockIdx.x * 2) * Cpart + c;
+      *reinterpret_cast<float4*>(o) = t;
+      *reinterpret_cast<float4*>(o + Cpart) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+}
+
+// The output of an encoder stage (conv -> BN -> ReLU -> y) feeds a skip connection and MaxPool2d(2): its gradient is dskip (full
+// resolution, may be absent) + the pooled gradient routed to the first maximum of each 2x2 window of y.  maxpool2_bwd_kernel
+// formed that sum in memory and the BatchNorm backward read it twice (1164 MB per level and step on average); here both stages of
+// the BatchNorm backward form it in registers: one thread per window and channel quad reads the window's four pre-BN values,
+// recomputes the four y's (bn_apply_relu_kernel's expression, so ties and all-zero windows route as in maxpool2_bwd_kernel), and
+// takes g = routed + dskip (that kernel's order).  Pixels of a last odd row / column belong to windows without a pooled value and
+// receive the skip term only.  grid = (window blocks, channel-quad blocks), block = rows x CQ, windows in ascending order per thread.
+// APPLY = false: partial rows part[blk][2][Cpart] of sum g * [y > 0] and sum g * [y > 0] * xhat; APPLY = true: dx.
+template <bool APPLY>
+__global__ __launch_bounds__(256) void bn_pool_bwd_kernel(const float* __restrict__ dskip, int ds_cs, int ds_coff,
+                                                          const float* __restrict__ dpool, int dp_cs, int dp_coff,
+                                                          const float* __restrict__ x, int x_cs, int x_coff, float* __restrict__ dx,
+                                                          int dx_cs, int dx_coff, const float* __restrict__ mean,
+                                                          const float* __restrict__ invstd, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, const float* __restrict__ sums, int N, int H,
+                                                          int W, int C, int Cw, int CQ, float* __restrict__ part, int Cpart) {
+  __shared__ float4 red[2][256];
+  const int rows = 256 / CQ;
+  const int cq = threadIdx.x % CQ, pr = threadIdx.x / CQ;
+  const int c = (blockIdx.y * CQ + cq) * 4;
+  const int WH = (H + 1) >> 1, WW = (W + 1) >> 1, OH = H >> 1, OW = W >> 1;
+  const unsigned nwin = (unsigned)N * WH * WW;
+  const unsigned per = (nwin + gridDim.x - 1) / gridDim.x;
+  const unsigned w0 = blockIdx.x * per;
+  const unsigned w1 = min(nwin, w0 + per);
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+  if (c < (APPLY ? Cw : C)) {
+    const float inv_np = 1.f / (float)(N * H * W);
+    float sc[4], sh[4], mu[4], is[4], k1[4], k2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool ok = c + j < C;
+      sc[j] = ok ? scale[c + j] : 0.f;
+      sh[j] = ok ? shift[c + j] : 0.f;
+      mu[j] = ok ? mean[c + j] : 0.f;
+      is[j] = ok ? invstd[c + j] : 0.f;
+      k1[j] = (ok && APPLY) ? sums[c + j] * inv_np : 0.f;
+      k2[j] = (ok && APPLY) ? sums[C + c + j] * inv_np : 0.f;
+    }
+    for (unsigned wi = w0 + pr; wi < w1; wi += rows) {
+      const int wx = (int)(wi % (unsigned)WW);
+      const unsigned r = wi / (unsigned)WW;
+      const int wy = (int)(r % (unsigned)WH), n = (int)(r / (unsigned)WH);
+      const int iy = 2 * wy, ix = 2 * wx;
+      const bool row1 = iy + 1 < H, col1 = ix + 1 < W, pooled = wy < OH && wx < OW;      // (pooled implies row1 && col1)
+      const long long pix = ((long long)n * H + iy) * W + ix;
+      // pixel m of the window: (iy + m / 2, ix + m % 2)
+#define HPRI_WIN_OK(m_) ((((m_) & 1) == 0 || col1) && (((m_) >> 1) == 0 || row1))
+#define HPRI_WIN_PIX(m_) (pix + ((m_) & 1) + (long long)((m_) >> 1) * W)
+      // all nine loads of the window are issued before the first use
+      float4 xv[4], dv[4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        xv[m] = HPRI_WIN_OK(m) ? *reinterpret_cast<const float4*>(x + HPRI_WIN_PIX(m) * x_cs + x_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        dv[m] = (dskip != nullptr && HPRI_WIN_OK(m)) ? *reinterpret_cast<const float4*>(dskip + HPRI_WIN_PIX(m) * ds_cs + ds_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      const float4 gp = pooled ? *reinterpret_cast<const float4*>(dpool + (((long long)n * OH + wy) * OW + wx) * dp_cs + dp_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float gq[4] = {gp.x, gp.y, gp.z, gp.w};
+      float xx[4][4], dd[4][4], o[4][4];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        xx[m][0] = xv[m].x; xx[m][1] = xv[m].y; xx[m][2] = xv[m].z; xx[m][3] = xv[m].w;
+        dd[m][0] = dv[m].x; dd[m][1] = dv[m].y; dd[m][2] = dv[m].z; dd[m][3] = dv[m].w;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float y[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) y[m] = (c + j < C) ? fmaxf(xx[m][j] * sc[j] + sh[j], 0.f) : 0.f;
+        const int k = first_argmax4(y[0], y[1], y[2], y[3]);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          float g = (pooled && k == m) ? gq[j] : 0.f;
+          if (dskip != nullptr) g += dd[m][j];
+          const float gj = (y[m] > 0.f) ? g : 0.f;
+          const float xh = (xx[m][j] - mu[j]) * is[j];
+          if (APPLY) {
+            o[m][j] = (c + j < C) ? sc[j] * (gj - k1[j] - xh * k2[j]) : 0.f;   // pad channels stay exactly zero
+          } else if (HPRI_WIN_OK(m)) {
+            s1[j] += gj;
+            s2[j] += gj * xh;
+          }
+        }
+      }
+      if (APPLY) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+          if (HPRI_WIN_OK(m)) *reinterpret_cast<float4*>(dx + HPRI_WIN_PIX(m) * dx_cs + dx_coff + c) = make_float4(o[m][0], o[m][1], o[m][2], o[m][3]);
+      }
+#undef HPRI_WIN_OK
+#undef HPRI_WIN_PIX
+    }
+  }
+  if (!APPLY) {
+    red[0][threadIdx.x] = make_float4(s1[0], s1[1], s1[2], s1[3]);
+    red[1][threadIdx.x] = make_float4(s2[0], s2[1], s2[2], s2[3]);
+    __syncthreads();
+    if (pr == 0 && c < Cpart) {
+      float4 t1 = make_float4(0.f, 0.f, 0.f, 0.f), t2 = t1;
+      for (int r = 0; r < rows; ++r) {
+        const float4 a = red[0][r * CQ + cq], b = red[1][r * CQ + cq];
+        t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
+        t2.x += b.x; t2.y += b.y; t2.z += b.z; t2.w += b.w;
+      }
+      float* o = part + ((size_t)blockIdx.x * 2) * Cpart + c;
+      *reinterpret_cast<float4*>(o) = t1;
+      *reinterpret_cast<float4*>(o + Cpart) = t2;
+    }
+  }
+}
+
+// y = relu(x * scale + shift) AND its MaxPool2d(2) map in one pass: one thread per 2x2 window and channel quad reads the window's
+// four pre-BN values, writes the four y's (bn_apply_relu_kernel's expression; pad channels zeros) and their maximum in
+// maxpool2_fwd_kernel's nesting: both outputs bit for bit those of the two passes.  Windows of a last odd row / column write y only.
+__global__ __launch_bounds__(256) void bn_apply_relu_pool_kernel(const float* __restrict__ x, int x_cs, int x_coff, float* __restrict__ y,
+                                                                 int y_cs, int y_coff, float* __restrict__ pool, int p_cs, int p_coff,
+                                                                 const float* __restrict__ scale, const float* __restrict__ shift, int N,
+                                                                 int H, int W, int C, int C4, int relu) {
+  const int WH = (H + 1) >> 1, WW = (W + 1) >> 1, OH = H >> 1, OW = W >> 1;
+  const unsigned total = (unsigned)N * WH * WW * C4;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int c = (int)(i % (unsigned)C4) * 4;
+    unsigned r = i / (unsigned)C4;
+    const int wx = (int)(r % (unsigned)WW); r /= (unsigned)WW;
+    const int wy = (int)(r % (unsigned)WH);
+    const int n = (int)(r / (unsigned)WH);
+    const int iy = 2 * wy, ix = 2 * wx;
+    const bool row1 = iy + 1 < H, col1 = ix + 1 < W, pooled = wy < OH && wx < OW;
+    const long long pix = ((long long)n * H + iy) * W + ix;
+    float sc[4], sh[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool ok = c + j < C;
+      sc[j] = ok ? scale[c + j] : 0.f;
+      sh[j] = ok ? shift[c + j] : 0.f;
+    }
+    float4 v[4], o[4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const bool okm = ((m & 1) == 0 || col1) && ((m >> 1) == 0 || row1);
+      v[m] = okm ? *reinterpret_cast<const float4*>(x + (pix + (m & 1) + (long long)(m >> 1) * W) * x_cs + x_coff + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      o[m].x = (c + 0 < C) ? v[m].x * sc[0] + sh[0] : 0.f; o[m].y = (c + 1 < C) ? v[m].y * sc[1] + sh[1] : 0.f;
+      o[m].z = (c + 2 < C) ? v[m].z * sc[2] + sh[2] : 0.f; o[m].w = (c + 3 < C) ? v[m].w * sc[3] + sh[3] : 0.f;
+      if (relu) { o[m].x = fmaxf(o[m].x, 0.f); o[m].y = fmaxf(o[m].y, 0.f); o[m].z = fmaxf(o[m].z, 0.f); o[m].w = fmaxf(o[m].w, 0.f); }
+      const bool okm = ((m & 1) == 0 || col1) && ((m >> 1) == 0 || row1);
+      if (okm) *reinterpret_cast<float4*>(y + (pix + (m & 1) + (long long)(m >> 1) * W) * y_cs + y_coff + c) = o[m];
+    }
+    if (pooled) {
+      float4 mx;
+      mx.x = fmaxf(fmaxf(o[0].x, o[1].x), fmaxf(o[2].x, o[3].x));
+      mx.y = fmaxf(fmaxf(o[0].y, o[1].y), fmaxf(o[2].y, o[3].y));
+      mx.z = fmaxf(fmaxf(o[0].z, o[1].z), fmaxf(o[2].z, o[3].z));
+      mx.w = fmaxf(fmaxf(o[0].w, o[1].w), fmaxf(o[2].w, o[3].w));
+      *reinterpret_cast<float4*>(pool + (((long long)n * OH + wy) * OW + wx) * p_cs + p_coff + c) = mx;
+    }
   }
 }
 
@@ -954,6 +1410,168 @@ extern "C" int hpri_outconv_bwd_x16(const float* dy, const float* target, const 
   return outconv_bwd_impl<true>(dy, target, gscale, reinterpret_cast<const float*>(x16), x_cs, x_coff, w, reinterpret_cast<float*>(dx),
                                 dx_cs, dx_coff, dx_cw, dx_accumulate, dw, db, accumulate_param_grads, workspace, ws_floats, N, P, C, K,
                                 stream, dx_bf16);
+}
+
+extern "C" int hpri_col_finalize(const float* part, int nblk, int Cpart, int C, float* sums, float* out1, float* out2,
+                                 int accumulate, float* zero_out, hipStream_t stream);      // bn.hip
+
+static inline size_t rup4(size_t v) { return (v + 3) & ~(size_t)3; }
+
+// Forward of  x -> BatchNorm (+ ReLU) -> y -> 1x1 head with ONE class  from the pre-BN tensor x (fp32, C <= 256): logits (N * P) and,
+// target != nullptr, the fp64 loss partials of hpri_outconv_fwd_bce (hpri_outconv_fwd_bce_blocks of them); y is not stored.
+extern "C" int hpri_bn_relu_outconv_fwd(const float* x, int x_cs, int x_coff, const float* scale, const float* shift, int relu,
+                                        const float* w, const float* b, float* y, const float* target, double* partial,
+                                        size_t partial_doubles, int N, long long P, int C, hipStream_t stream) {
+  HPRI_REQUIRE(x && scale && shift && w && y && N > 0 && P > 0 && C > 0 && C <= 256, "bn_relu_outconv_fwd: bad arguments");
+  HPRI_REQUIRE(target == nullptr || partial != nullptr, "bn_relu_outconv_fwd: a target needs the partial buffer");
+  HPRI_REQ_V4(x_cs, x_coff);
+  HPRI_REQUIRE(((C + 3) / 4) * 4 + x_coff <= x_cs, "bn_relu_outconv_fwd: channel stride too small for 4-channel reads");
+  const int nb = ew_blocks((long long)N * P * 16);
+  if (target != nullptr && (size_t)nb > partial_doubles) return hpri_set_error(HPRI_ERR_WORKSPACE, "bn_relu_outconv_fwd: partial buffer too small");
+  const int nj = (((C + 3) >> 2) + 15) >> 4;
+#define HPRI_BOF(BCE_, NJ_)                                                                                                        \
+  hipLaunchKernelGGL((bn_outconv_fwd_kernel<BCE_, NJ_>), dim3(nb), dim3(256), 0, stream, x, x_cs, x_coff, scale, shift, relu, w, b, y, \
+                     (long long)N * P, C, target, partial)
+  if (target != nullptr) { if (nj == 1) HPRI_BOF(true, 1); else if (nj == 2) HPRI_BOF(true, 2); else HPRI_BOF(true, 4); }
+  else { if (nj == 1) HPRI_BOF(false, 1); else if (nj == 2) HPRI_BOF(false, 2); else HPRI_BOF(false, 4); }
+#undef HPRI_BOF
+  HPRI_CHECK_LAUNCH();
+  return HPRI_OK;
+}
+
+// workspace floats of hpri_bn_relu_outconv_bwd: three sets of partial rows (BatchNorm sums, dx column sums, head) + two sum rows
+extern "C" size_t hpri_bn_relu_outconv_bwd_ws(int N, long long P, int C) {
+  int nblk, Cpart;
+  hpri_outconv_bwd_plan(N, P, C, 1, &nblk, &Cpart);
+  return 3 * (size_t)nblk * 2 * Cpart + 2 * rup4(2 * (size_t)C);
+}
+
+// Backward of  x -> BatchNorm (+ ReLU) -> y -> 1x1 head with ONE class  in two sweeps of the pre-BN tensor x (fp32): dx, dgamma,
+// dbeta, the bias gradient of the convolution in front (dbias, as hpri_bn_relu_bwd) and the head's dw / db, without the head's
+// input gradient or y in memory (kernels above).  `dy` = the logit gradient (N*P), or -- target != nullptr -- the LOGITS, the
+// gradient of the mean BCE-with-logits loss being formed inside as hpri_outconv_bwd_bce does (gscale, hpri_set_loss_scale).
+// One statistics group; the per-block partial sums and both finalize kernels are those of hpri_outconv_bwd(_bce) followed by
+// hpri_bn_relu_bwd, so every result equals that route's bit for bit.
+extern "C" int hpri_bn_relu_outconv_bwd(const float* dy, const float* target, const float* gscale, const float* x, int x_cs, int x_coff,
+                                        const float* w, float* dx, int dx_cs, int dx_coff, int Cw, const float* mean,
+                                        const float* invstd, const float* scale, const float* shift, float* dgamma, float* dbeta,
+                                        int accumulate_bn_grads, float* dbias, int accumulate_dbias, float* dw, float* db,
+                                        int accumulate_head_grads, float* workspace, size_t ws_floats, int N, long long P, int C,
+                                        int relu, int use_batch_stats, hipStream_t stream) {
+  HPRI_REQUIRE(dy && x && w && dx && mean && invstd && scale && shift && dw && workspace, "bn_relu_outconv_bwd: null pointer");
+  HPRI_REQUIRE(N > 0 && P > 0 && C > 0 && C <= 1024 && (long long)N * P < (1ll << 31), "bn_relu_outconv_bwd: bad sizes");
+  HPRI_REQ_V4(x_cs, x_coff); HPRI_REQ_V4(dx_cs, dx_coff);
+  HPRI_REQUIRE(Cw % 4 == 0 && Cw >= C && Cw + x_coff <= x_cs && Cw + dx_coff <= dx_cs, "bn_relu_outconv_bwd: channel layout");
+  if (hpri_bn_relu_outconv_bwd_ws(N, P, C) > ws_floats) return hpri_set_error(HPRI_ERR_WORKSPACE, "bn_relu_outconv_bwd: workspace too small");
+  int nblk, Cpart;
+  hpri_outconv_bwd_plan(N, P, C, 1, &nblk, &Cpart);          // (= hpri_col_reduce_plan(N * P, 1, C) for C <= 1024)
+  const size_t rowsz = (size_t)nblk * 2 * Cpart, sumsz = rup4(2 * (size_t)C);
+  float* bnpart = workspace;
+  float* sums = bnpart + rowsz;
+  float* dxpart = sums + sumsz;
+  float* dxsums = dxpart + rowsz;
+  float* hwpart = dxsums + sumsz;
+  const long long NP = (long long)N * P;
+  const int c4 = hpri_cdiv(C, 4), cq = pick_cq(c4), ycols = hpri_cdiv(c4, cq), ycols_w = hpri_cdiv(Cw >> 2, cq);
+  const float ls = hpri_loss_scale();
+  if (target != nullptr)
+    hipLaunchKernelGGL(bn_head_reduce_kernel<true>, dim3(nblk, ycols), dim3(256), 0, stream, dy, target, gscale, ls, x, x_cs, x_coff, w,
+                       mean, invstd, scale, shift, NP, C, cq, relu, bnpart, hwpart, Cpart);
+  else
+    hipLaunchKernelGGL(bn_head_reduce_kernel<false>, dim3(nblk, ycols), dim3(256), 0, stream, dy, target, gscale, ls, x, x_cs, x_coff, w,
+                       mean, invstd, scale, shift, NP, C, cq, relu, bnpart, hwpart, Cpart);
+  HPRI_CHECK_LAUNCH();
+  // the head's parameters first (the order of the two-call route), then the BatchNorm sums
+  hipLaunchKernelGGL(outconv_bwd_weight_finalize_kernel, dim3(C + 1), dim3(256), 0, stream, hwpart, nblk, 1, Cpart, C, dw, db,
+                     accumulate_head_grads);
+  HPRI_CHECK_LAUNCH();
+  const bool pg = dgamma != nullptr && dbeta != nullptr;
+  const bool dbias_zero = dbias != nullptr && use_batch_stats;       // exactly zero in training mode (see bn.hip: bn_relu_bwd_impl)
+  int rc = hpri_col_finalize(bnpart, nblk, Cpart, C, sums, pg ? dbeta : nullptr, pg ? dgamma : nullptr, accumulate_bn_grads,
+                             (dbias_zero && !accumulate_dbias) ? dbias : nullptr, stream);
+  if (rc != HPRI_OK) return rc;
+  if (dbias_zero) dbias = nullptr;
+  if (target != nullptr)
+    hipLaunchKernelGGL(bn_head_apply_kernel<true>, dim3(nblk, ycols_w), dim3(256), 0, stream, dy, target, gscale, ls, x, x_cs, x_coff, w,
+                       dx, dx_cs, dx_coff, mean, invstd, scale, shift, sums, (int)NP, C, Cw, cq, relu, use_batch_stats,
+                       dbias != nullptr ? dxpart : nullptr, Cpart);
+  else
+    hipLaunchKernelGGL(bn_head_apply_kernel<false>, dim3(nblk, ycols_w), dim3(256), 0, stream, dy, target, gscale, ls, x, x_cs, x_coff, w,
+                       dx, dx_cs, dx_coff, mean, invstd, scale, shift, sums, (int)NP, C, Cw, cq, relu, use_batch_stats,
+                       dbias != nullptr ? dxpart : nullptr, Cpart);
+  HPRI_CHECK_LAUNCH();
+  if (dbias != nullptr) {
+    rc = hpri_col_finalize(dxpart, nblk, Cpart, C, dxsums, dbias, nullptr, accumulate_dbias, nullptr, stream);
+    if (rc != HPRI_OK) return rc;
+  }
+  return HPRI_OK;
+}
+
+// (window blocks, row width) of hpri_bn_relu_bwd_pool's reduction; workspace floats = nblk * 2 * Cpart + 2 * C
+extern "C" int hpri_bn_relu_bwd_pool_plan(int N, int H, int W, int C, int* nblk, int* Cpart) {
+  const int c4 = hpri_cdiv(C, 4), cq = pick_cq(c4), rows = 256 / cq, ycols = hpri_cdiv(c4, cq);
+  const long long nwin = (long long)N * ((H + 1) / 2) * ((W + 1) / 2);
+  long long nb = 1024 / ycols;
+  const long long maxb = (nwin + rows * 2 - 1) / (rows * 2);
+  if (nb > maxb) nb = maxb;
+  if (nb < 1) nb = 1;
+  *nblk = (int)nb; *Cpart = ycols * cq * 4;
+  return HPRI_OK;
+}
+
+// Training-mode BatchNorm + ReLU backward of a stage whose output y (N x H x W) feeds MaxPool2d(2) and, optionally, a skip
+// connection: the gradient of y is given as its two terms, dskip (full resolution; NULL: none) and dpool (N x H/2 x W/2), and is
+// never stored (bn_pool_bwd_kernel).  dx, dgamma, dbeta as hpri_bn_relu_bwd with relu = 1, use_batch_stats = 1, one group; dbias
+// (the bias of the convolution in front: an exactly zero gradient) is cleared unless accumulate_dbias.
+extern "C" int hpri_bn_relu_bwd_pool(const float* dskip, int ds_cs, int ds_coff, const float* dpool, int dp_cs, int dp_coff,
+                                     const float* x, int x_cs, int x_coff, float* dx, int dx_cs, int dx_coff, const float* mean,
+                                     const float* invstd, const float* scale, const float* shift, float* dgamma, float* dbeta,
+                                     int accumulate_param_grads, float* dbias, int accumulate_dbias, float* workspace,
+                                     size_t ws_floats, int N, int H, int W, int C, int Cw, hipStream_t stream) {
+  HPRI_REQUIRE(dpool && x && dx && mean && invstd && scale && shift && workspace, "bn_relu_bwd_pool: null pointer");
+  HPRI_REQUIRE(N > 0 && H >= 2 && W >= 2 && C > 0 && C <= 1024 && (long long)N * H * W < (1ll << 31), "bn_relu_bwd_pool: bad sizes");
+  HPRI_REQ_V4(x_cs, x_coff); HPRI_REQ_V4(dx_cs, dx_coff); HPRI_REQ_V4(dp_cs, dp_coff);
+  HPRI_REQUIRE(Cw % 4 == 0 && Cw >= C && Cw + x_coff <= x_cs && Cw + dx_coff <= dx_cs && Cw + dp_coff <= dp_cs,
+               "bn_relu_bwd_pool: channel layout");
+  if (dskip != nullptr) {
+    HPRI_REQ_V4(ds_cs, ds_coff);
+    HPRI_REQUIRE(Cw + ds_coff <= ds_cs, "bn_relu_bwd_pool: channel layout of the skip gradient");
+  }
+  int nblk, Cpart;
+  hpri_bn_relu_bwd_pool_plan(N, H, W, C, &nblk, &Cpart);
+  if ((size_t)nblk * 2 * Cpart + 2 * (size_t)C > ws_floats) return hpri_set_error(HPRI_ERR_WORKSPACE, "bn_relu_bwd_pool: workspace too small");
+  float* part = workspace;
+  float* sums = workspace + (size_t)nblk * 2 * Cpart;
+  const int c4 = hpri_cdiv(C, 4), cq = pick_cq(c4), ycols = hpri_cdiv(c4, cq), ycols_w = hpri_cdiv(Cw >> 2, cq);
+  hipLaunchKernelGGL(bn_pool_bwd_kernel<false>, dim3(nblk, ycols), dim3(256), 0, stream, dskip, ds_cs, ds_coff, dpool, dp_cs, dp_coff, x,
+                     x_cs, x_coff, dx, dx_cs, dx_coff, mean, invstd, scale, shift, (const float*)nullptr, N, H, W, C, Cw, cq, part, Cpart);
+  HPRI_CHECK_LAUNCH();
+  const bool pg = dgamma != nullptr && dbeta != nullptr;
+  const int rc = hpri_col_finalize(part, nblk, Cpart, C, sums, pg ? dbeta : nullptr, pg ? dgamma : nullptr, accumulate_param_grads,
+                                   (dbias != nullptr && !accumulate_dbias) ? dbias : nullptr, stream);
+  if (rc != HPRI_OK) return rc;
+  hipLaunchKernelGGL(bn_pool_bwd_kernel<true>, dim3(nblk, ycols_w), dim3(256), 0, stream, dskip, ds_cs, ds_coff, dpool, dp_cs, dp_coff, x,
+                     x_cs, x_coff, dx, dx_cs, dx_coff, mean, invstd, scale, shift, (const float*)sums, N, H, W, C, Cw, cq,
+                     (float*)nullptr, Cpart);
+  HPRI_CHECK_LAUNCH();
+  return HPRI_OK;
+}
+
+// BatchNorm apply (+ ReLU) of a stage whose output y (N x H x W, channels [C, Cw) zeros) is max-pooled next: y and the pooled map
+// (N x H/2 x W/2, same pad rule) in one pass over the pre-BN tensor; fp32, one statistics group.  Both bit-equal to
+// hpri_bn_apply_relu followed by hpri_maxpool2_fwd.
+extern "C" int hpri_bn_apply_relu_pool(const float* x, int x_cs, int x_coff, float* y, int y_cs, int y_coff, float* pool, int p_cs,
+                                       int p_coff, const float* scale, const float* shift, int N, int H, int W, int C, int Cw, int relu,
+                                       hipStream_t stream) {
+  HPRI_REQUIRE(x && y && pool && scale && shift && N > 0 && H >= 2 && W >= 2 && C > 0, "bn_apply_relu_pool: bad arguments");
+  HPRI_REQ_V4(x_cs, x_coff); HPRI_REQ_V4(y_cs, y_coff); HPRI_REQ_V4(p_cs, p_coff);
+  HPRI_REQUIRE(Cw % 4 == 0 && Cw >= C && Cw + x_coff <= x_cs && Cw + y_coff <= y_cs && Cw + p_coff <= p_cs, "bn_apply_relu_pool: channel layout");
+  const long long windows = (long long)N * ((H + 1) / 2) * ((W + 1) / 2) * (Cw / 4);
+  HPRI_REQUIRE(windows < (1ll << 31), "bn_apply_relu_pool: more than 2^31 window quads");
+  hipLaunchKernelGGL(bn_apply_relu_pool_kernel, dim3(ew_blocks(windows)), dim3(256), 0, stream, x, x_cs, x_coff, y, y_cs, y_coff, pool,
+                     p_cs, p_coff, scale, shift, N, H, W, C, Cw / 4, relu);
+  HPRI_CHECK_LAUNCH();
+  return HPRI_OK;
 }
 
 extern "C" int hpri_synth_fill(float* dst, long long n, unsigned long long seed, int mode, float thr, float scale,

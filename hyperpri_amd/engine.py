@@ -195,7 +195,7 @@ class Act:
 
     Invariant: channels [C, cw) (cw = C rounded up to 8) exist inside the stride and hold zeros, so
     consumers may run their K loop over ``cw`` channels."""
-    __slots__ = ("buf", "N", "H", "W", "C", "cs", "coff", "pl", "parent", "f32_valid", "want_pl", "pl_part", "colsum_req", "b16", "bn_src", "cat_pl", "up_slice", "yr16", "skip_g16", "raw")
+    __slots__ = ("buf", "N", "H", "W", "C", "cs", "coff", "pl", "parent", "f32_valid", "want_pl", "pl_part", "colsum_req", "b16", "bn_src", "cat_pl", "up_slice", "yr16", "skip_g16", "raw", "lazy_bn", "pooled")
 
     def __init__(self, buf: torch.Tensor, N: int, H: int, W: int, C: int, cs: int, coff: int = 0):
         self.buf, self.N, self.H, self.W, self.C, self.cs, self.coff = buf, N, H, W, C, cs, coff
@@ -212,6 +212,8 @@ class Act:
         self.yr16 = False                       # the pre-BN tensor behind this one is stored as bf16 (its BatchNorm backward can read a bf16 gradient)
         self.skip_g16 = False                   # a decoder concat whose skip half's gradient is stored as bf16 rows (SKIP_GRAD_BF16)
         self.raw = None                         # (caller's NCHW tensor, planes for the layout pass): not laid out yet (Act.raw_nchw)
+        self.pooled = None                      # MaxPool2d(2) of this tensor, written by the BatchNorm-apply pass that produced it (FUSE_POOL_FWD); maxpool2 takes it
+        self.lazy_bn = None                     # (pre-BN Act, scale, shift, relu): BN(+ReLU) of that tensor, not computed and without storage (FUSE_HEAD_BN; _materialize_bn)
 
     @property
     def cw(self) -> int:
@@ -499,6 +501,9 @@ class Tape:
         self.colsum: Dict[int, tuple] = {}          # id(Act) -> (stats records, tiles, Cpad, c0) left by the data-gradient kernel that wrote its gradient
         self.gupl: Dict[int, tuple] = {}            # id(Act) -> (Planes of the gradient of a concat's upsampled half, fp32 form absent?)
         self.bnpart: Dict[int, tuple] = {}          # id(Act) -> (partial sums, blocks, Cpart) of its BatchNorm backward, left by the same kind of kernel
+        self.bnstage: Dict[int, object] = {}        # id(Act) -> the fp32 conv -> BN (-> ReLU) stage recorded on this tape whose output the Act is
+        self.headpend: Dict[int, object] = {}       # id(Act) -> the head's logit-gradient source, waiting for the BatchNorm backward of the stage that made the Act (FUSE_HEAD_BN)
+        self.poolpend: Dict[int, Act] = {}          # id(Act) -> gradient of its max-pooled map, waiting likewise (FUSE_POOL_BN)
         self.uses: Dict[int, int] = {}              # id(parameter) -> ops recorded on this tape that will produce a gradient for it
         self._touched: List[int] = []               # parameters the running node asked a gradient slot for
         self.delivered: set = set()                 # segmented tape: parameters whose gradient has left with an earlier slice
@@ -673,6 +678,9 @@ class Tape:
         self.uses.clear()
         self.colsum.clear()
         self.bnpart.clear()
+        self.bnstage.clear()
+        self.headpend.clear()
+        self.poolpend.clear()
         self.gupl.clear()
         self.delivered.clear()
         self._acc_into.clear()
@@ -1068,7 +1076,7 @@ def conv_bn_relu(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.
                  train: bool, ks: int, groups: int = 1, relu: bool = True, need_dx: bool = True,
                  precision: Optional[str] = None, room: int = 0, next_cout: int = 0, cat_room: int = 0,
                  cat_into: Optional[Act] = None, k_gap: Optional[Tuple[int, int]] = None, planes_only: bool = False,
-                 out_planes: bool = False, head_next: bool = False, relu_without_bn: bool = False) -> Act:
+                 out_planes: bool = False, head_next: bool = False, relu_without_bn: bool = False, pool_next: bool = False) -> Act:
     """Conv2d(k=ks, pad=ks//2) -> BatchNorm -> ReLU  (model_parts.py:22-27; models.py:169-180 with the
     Conv3d weight (F,1,D,3,3) read as (F,D,3,3); models.py:108-114 for Linear -> BatchNorm1d -> ReLU with
     ks = 1 and ``groups`` = images, each image being its own BN batch, models.py:132).
@@ -1115,12 +1123,17 @@ def conv_bn_relu(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.
     if bn is None:
         c.y, c.st = c.yr, None
     else:
-        _bn_forward(c, room, next_cout, cat_room, cat_into, planes_only, out_planes, head_next)
+        # the head is the only reader (the caller says so) and reads the pre-BN tensor itself (out_conv): no apply pass, no storage
+        defer = bool(tape.record and head_next and FUSE_HEAD_BN and prec == "fp32" and groups == 1 and room == 0 and cout <= 256
+                     and not c.yr16 and not (c.v2 or c.g3) and not cat_room and cat_into is None and not planes_only and not out_planes)
+        _bn_forward(c, room, next_cout, cat_room, cat_into, planes_only, out_planes, head_next, defer, pool_next)
     y = c.y
     if not tape.record:
         return y
     if bn is not None and next_cout > 0 and groups == 1 and room == 0:
         y.bn_src = (c.yr, c.st, relu)          # one consumer (the caller says so): its data-gradient kernel may do this stage's reduction
+    elif bn is not None and prec == "fp32" and groups == 1 and not c.yr16 and (y.f32_valid or y.lazy_bn is not None) and cout <= 1024:
+        tape.bnstage[id(y)] = c                # the head / max-pooling may leave their gradient term to this stage's BatchNorm backward
     tape.note_params(weight, bias, *((bn.weight, bn.bias) if bn is not None else ()))
     tape.nodes.append(lambda tp: _conv_backward(tp, c))
     return y
@@ -1205,7 +1218,7 @@ def _conv_forward(c) -> None:
 
 
 def _bn_forward(c, room: int, next_cout: int, cat_room: int, cat_into: Optional[Act], planes_only: bool, out_planes: bool,
-                head_next: bool = False) -> None:
+                head_next: bool = False, defer: bool = False, pool_next: bool = False) -> None:
     """BatchNorm finalize (batch statistics from the conv epilogue's records, or the running ones) + normalise + ReLU.  Leaves
     c.y (the stage's output, with its bf16 planes where a plane reader follows) and c.st (mean, invstd, var, scale, shift)."""
     global _BN_EPOCH
@@ -1221,6 +1234,12 @@ def _bn_forward(c, room: int, next_cout: int, cat_room: int, cat_into: Optional[
     else:
         _lib.call("hpri_bn_eval_prepare", _p(bn.running_mean), _p(bn.running_var), _p(bn.weight), _p(bn.bias),
                   bn.eps, cout, _p(mean), _p(invstd), _p(scale), _p(shift), _stream())
+    if defer:
+        # ``defer``: the result is left as (pre-BN tensor, scale, shift, relu) -- the pattern of Act.raw_nchw
+        y = Act(torch.empty(8, dtype=torch.float32, device=dev), x.N, x.H, x.W, cout, _rup(cout, 8), 0)
+        y.f32_valid, y.lazy_bn = False, (yr, scale, shift, int(c.relu))
+        c.y, c.st = y, st
+        return
     y = Act.new_with_room(x.N, x.H, x.W, cout, room, dev)    # room > 0: a skip tensor, written where its concat needs it
     ppg = (x.P // G)
     # bf16 plane mode: the normalise pass also writes y as bf16 planes -- what the next 3x3 convolution (and the
@@ -1269,6 +1288,17 @@ def _bn_forward(c, room: int, next_cout: int, cat_room: int, cat_into: Optional[
     if (ypl is not None and next_cout > 0 and PLANES_ONLY_ACT and PLANE_WGRAD and room == 0
             and _planes_fit(y, max(cout, next_cout))):
         y.f32_valid = False
+    if (pool_next and FUSE_POOL_FWD and c.prec == "fp32" and not c.yr16 and G == 1 and ypl is None and cpl is None and y.f32_valid
+            and x.H >= 2 and x.W >= 2):
+        # ``pool_next``: a MaxPool2d(2) reads the result next (the caller says so): the pass writes the pooled map as well,
+        # window by window (``maxpool2`` finds it on the Act and launches nothing)
+        pooled = Act.new(x.N, x.H // 2, x.W // 2, cout, dev)
+        _lib.call("hpri_bn_apply_relu_pool", yr.ptr, yr.cs, yr.coff, y.ptr, y.cs, y.coff, pooled.ptr, pooled.cs, pooled.coff,
+                  _p(scale), _p(shift), x.N, x.H, x.W, cout, y.cw, int(c.relu), _stream())
+        y.pooled = pooled
+        y.yr16 = False
+        c.y, c.st = y, st
+        return
     _lib.call("hpri_bn_apply_relu_x16" if c.yr16 else "hpri_bn_apply_relu_pl", yr.ptr, yr.cs, yr.coff,
               y.ptr if y.f32_valid else ctypes.c_void_p(0), y.cs, y.coff,
               _p(scale), _p(shift),
@@ -1278,11 +1308,35 @@ def _bn_forward(c, room: int, next_cout: int, cat_room: int, cat_into: Optional[
     c.y, c.st = y, st
 
 
+def _materialize_bn(y: Act) -> Act:
+    """Give a deferred BN(+ReLU) result (``Act.lazy_bn``) its fp32 storage: the apply pass its producer skipped."""
+    yr, scale, shift, relu = y.lazy_bn
+    y.buf = torch.empty(y.P * y.cs, dtype=torch.float32, device=yr.buf.device)
+    _lib.call("hpri_bn_apply_relu_pl", yr.ptr, yr.cs, yr.coff, y.ptr, y.cs, y.coff, _p(scale), _p(shift), y.P, y.P, y.C, y.cw, relu,
+              ctypes.c_void_p(0), 0, 0, 0, 0, 0, _stream())
+    y.f32_valid, y.lazy_bn = True, None
+    return y
+
+
+def _skip_grad_fits(g: Act) -> bool:
+    """hpri_bn_relu_bwd_pool reads the skip gradient in 16-byte pieces over the padded width: the view must hold them."""
+    return (not g.b16) and g.f32_valid and g.cs % 4 == 0 and g.coff % 4 == 0 and g.cw + g.coff <= g.cs
+
+
 def _conv_backward(tp: Tape, c) -> None:
+    tp.bnstage.pop(id(c.y), None)          # (the table must not keep the stage's tensors alive beyond its own backward)
+    head, pool = tp.headpend.pop(id(c.y), None), tp.poolpend.pop(id(c.y), None)
+    if head is not None and (id(c.y) in tp.grads or pool is not None):
+        # the head was not the only consumer after all: its gradient goes to memory like everybody else's (the two-call route)
+        head.classic(tp)
+        head = None
+    if pool is not None and id(c.y) in tp.grads and not _skip_grad_fits(tp.grads[id(c.y)]):
+        _pool_bwd_classic(tp, c.y, pool)
+        pool = None
     g = tp.grads.pop(id(c.y), None)
-    if g is None:
+    if g is None and head is None and pool is None:
         return
-    dyr = _conv_bwd_bn(tp, c, g)
+    dyr = _conv_bwd_bn_fused(tp, c, g, head, pool) if (head is not None or pool is not None) else _conv_bwd_bn(tp, c, g)
     _conv_bwd_weight(tp, c, dyr)
     if c.need_dx:
         _conv_bwd_data(tp, c, dyr)
@@ -1328,6 +1382,64 @@ def _conv_bwd_bn(tp: Tape, c, g: Act) -> Act:
               _p(mean), _p(invstd), _p(scale), _p(shift), _p(dgam), _p(dbet), acc_g, _p(db), acc_b,
               _p(ws), ws.numel(), x.P, x.P // G, cout, dyr.cw, int(c.relu), int(c.use_batch), *_pl_args(dpl), _stream())
     return dyr
+
+
+# fp32 mode: gradient terms that are cheap to form are not written for the BatchNorm backward to read; its two sweeps form them.
+# (Module attributes under the HPRI_FUSIONS master switch.)
+# FUSE_HEAD_BN: the one-class head's input gradient dlogit[p] * w[c] and its weight gradient's read of the last activation
+# (hpri_bn_relu_outconv_bwd: 2.1 -> 0.9 GB per CubeNET-64 step).
+FUSE_HEAD_BN = FUSIONS
+# FUSE_POOL_BN: the max-pooling backward of an encoder stage's output, summed with the skip gradient (hpri_bn_relu_bwd_pool:
+# 1164 -> 775 MB per level).
+FUSE_POOL_BN = FUSIONS
+# FUSE_POOL_FWD: the BatchNorm-apply pass of an encoder stage also writes the max-pooled map (hpri_bn_apply_relu_pool): the pooling
+# pass does not read the activation again (4 x 141 MB and four launches per CubeNET-64 step).
+FUSE_POOL_FWD = FUSIONS
+
+
+def _conv_bwd_bn_fused(tp: Tape, c, g: Optional[Act], head, pool: Optional[Act]) -> Act:
+    """``_conv_bwd_bn`` for a stage whose output gradient is not in memory: ``head`` (the logit-gradient source the 1x1 head left,
+    ``out_conv``) or ``pool`` (the gradient of the max-pooled map, ``maxpool2``) + ``g`` (the skip gradient, or None)."""
+    x, bn, bias, dev, cout = c.x, c.bn, c.bias, c.dev, c.cout
+    dyr = Act.new(x.N, x.H, x.W, cout, dev)
+    st, yr = c.st, c.yr
+    mean, invstd, varu, scale, shift = (st[i * cout:(i + 1) * cout] for i in range(5))
+    if head is not None:
+        # the head's parameters take their slots first: the order in which a gradient sink hears of them is the two-call route's.
+        # They are taken inside THIS stage's tape node: under the segmented chain (autograd.run_staged) that needs the head in the
+        # same stage as this convolution -- every network's ``_stages()`` appends ``outc`` to its last stage; a stage cut between
+        # the two would make ``param_slot`` raise ("listed under the wrong stage") rather than lose a gradient
+        dw, acc_w = tp.param_slot(head.weight)
+        dbh = tp.param_slot(head.bias)[0] if head.bias is not None else None
+    dgam, acc_g = tp.param_slot(bn.weight)
+    dbet, _ = tp.param_slot(bn.bias)
+    db, acc_b = (tp.param_slot(bias) if bias is not None else (None, 0))
+    if head is not None:
+        ws = _ws(_lib.current().hpri_bn_relu_outconv_bwd_ws(x.N, x.H * x.W, cout), dev)
+        _lib.call("hpri_bn_relu_outconv_bwd", _p(head.gy), _p(head.tgt), _p(head.gs), yr.ptr, yr.cs, yr.coff, _p(head.weight),
+                  dyr.ptr, dyr.cs, dyr.coff, dyr.cw, _p(mean), _p(invstd), _p(scale), _p(shift), _p(dgam), _p(dbet), acc_g,
+                  _p(db), acc_b, _p(dw), _p(dbh), acc_w, _p(ws), ws.numel(), x.N, x.H * x.W, cout, int(c.relu), int(c.use_batch),
+                  _stream())
+        return dyr
+    nblk = ctypes.c_int(); cpart = ctypes.c_int()
+    _lib.call("hpri_bn_relu_bwd_pool_plan", x.N, x.H, x.W, cout, ctypes.byref(nblk), ctypes.byref(cpart))
+    ws = _ws(nblk.value * 2 * cpart.value + 2 * cout, dev)
+    _lib.call("hpri_bn_relu_bwd_pool", g.ptr if g is not None else ctypes.c_void_p(0), g.cs if g is not None else 0,
+              g.coff if g is not None else 0, pool.ptr, pool.cs, pool.coff, yr.ptr, yr.cs, yr.coff, dyr.ptr, dyr.cs, dyr.coff,
+              _p(mean), _p(invstd), _p(scale), _p(shift), _p(dgam), _p(dbet), acc_g, _p(db), acc_b, _p(ws), ws.numel(),
+              x.N, x.H, x.W, cout, dyr.cw, _stream())
+    return dyr
+
+
+def _pool_bwd_classic(tp: Tape, x: Act, g: Act) -> None:
+    """MaxPool2d(2) backward into the gradient table (fp32 input): g = gradient of the pooled map of ``x``."""
+    gx, acc = tp.grad_slot(x, b16_ok=True)
+    if gx.b16:
+        _lib.call("hpri_maxpool2_bwd_x16", x.ptr, 0, x.cs, x.coff, g.ptr, g.cs, g.coff, gx.ptr, 1, gx.cs, gx.coff,
+                  x.N, x.H, x.W, _rup(x.C, 4), int(acc), _stream())
+    else:
+        _lib.call("hpri_maxpool2_bwd", x.ptr, x.cs, x.coff, g.ptr, g.cs, g.coff, gx.ptr, gx.cs, gx.coff,
+                  x.N, x.H, x.W, _rup(x.C, 4), int(acc), _stream())
 
 
 def _conv_bwd_weight(tp: Tape, c, dyr: Act) -> None:
@@ -1801,12 +1913,16 @@ def maxpool2(tape: Tape, x: Act) -> Act:
     npl = x.pl.npl if x.pl is not None else x.want_pl
     # ... and as planes ONLY when its input was: the pooled map's readers are then the next DoubleConv's plane kernels
     only = x16 and npl == 1 and PLANE_PRODUCERS and _planes_fit(Act(x.buf, x.N, x.H // 2, x.W // 2, 2 * x.C, 2 * x.C), 2 * x.C)
+    ready = x.pooled if (not x16 and not only and npl == 0) else None       # written by the producer's BatchNorm-apply pass
+    x.pooled = None
     y = (Act(torch.empty(8, dtype=torch.float32, device=dev), x.N, x.H // 2, x.W // 2, x.C, _rup(x.C, 8), 0) if only
-         else Act.new(x.N, x.H // 2, x.W // 2, x.C, dev))
+         else (ready if ready is not None else Act.new(x.N, x.H // 2, x.W // 2, x.C, dev)))
     ypl = new_planes(y, npl) if (npl > 0 and PLANE_PRODUCERS) else None
     y.want_pl = npl
     y.f32_valid = not only
-    if x16:
+    if ready is not None:
+        pass
+    elif x16:
         _lib.call("hpri_maxpool2_fwd_x16", _p(x.pl.buf), x.pl.cs, x.pl.coff, ctypes.c_void_p(0) if only else y.ptr, y.cs, y.coff,
                   x.N, x.H, x.W, _rup(x.C, 4), *_pl_args(ypl), _stream())
     else:
@@ -1815,6 +1931,13 @@ def maxpool2(tape: Tape, x: Act) -> Act:
         def bwd(tp: Tape) -> None:
             g = tp.grads.pop(id(y), None)
             if g is None:
+                return
+            st = tp.bnstage.get(id(x))
+            if (FUSE_POOL_BN and not x16 and st is not None and st.relu and st.use_batch and id(x) not in tp.poolpend
+                    and id(x) not in tp.headpend and _skip_grad_fits(g)):
+                # the output of a conv -> BN -> ReLU stage still to run its backward on this tape: that stage's BatchNorm
+                # backward routes this gradient itself (_conv_bwd_bn_fused); nothing is written here
+                tp.poolpend[id(x)] = g
                 return
             gx, acc = tp.grad_slot(x, b16_ok=True)
             if x16 or gx.b16:
@@ -2296,8 +2419,11 @@ def out_conv(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.Tens
     if C != x.C:
         raise RuntimeError(f"hyperpri_amd: out conv expects {C} channels, got {x.C}")
     dev = x.buf.device
+    if x.lazy_bn is not None and not (K == 1 and not k_gap and tape.record and FUSE_HEAD_BN and C <= 256):
+        _materialize_bn(x)
+    lazy = x.lazy_bn                # (pre-BN tensor, scale, shift, relu): the head forms BN + ReLU itself (hpri_bn_relu_outconv_fwd)
     x16 = x.pl is not None and not x.f32_valid
-    if not x.f32_valid and x.pl is None:
+    if not x.f32_valid and x.pl is None and lazy is None:
         raise RuntimeError("hyperpri_amd: internal error: a planes-only activation without planes reached the head")
     if k_gap and not x16:
         raise RuntimeError("hyperpri_amd: internal error: a gapped concat reaches the head on planes only")
@@ -2318,14 +2444,21 @@ def out_conv(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.Tens
         nblk = _lib.load().hpri_outconv_fwd_bce_blocks(x.N, x.H * x.W)
         part = torch.empty(nblk, dtype=torch.float64, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        _lib.call("hpri_outconv_fwd_x16" if x16 else "hpri_outconv_fwd_bce", *xa, _p(wsrc), _p(bias), _p(y), _p(tgt), _p(part), nblk,
-                  x.N, x.H * x.W, C, K, _stream())
+        if lazy is not None:
+            _lib.call("hpri_bn_relu_outconv_fwd", lazy[0].ptr, lazy[0].cs, lazy[0].coff, _p(lazy[1]), _p(lazy[2]), lazy[3], _p(weight),
+                      _p(bias), _p(y), _p(tgt), _p(part), nblk, x.N, x.H * x.W, C, _stream())
+        else:
+            _lib.call("hpri_outconv_fwd_x16" if x16 else "hpri_outconv_fwd_bce", *xa, _p(wsrc), _p(bias), _p(y), _p(tgt), _p(part), nblk,
+                      x.N, x.H * x.W, C, K, _stream())
         _lib.call("hpri_bce_finish", _p(part), nblk, y.numel(), _p(loss), _stream())
         # a DETACHED alias of the logits (same storage, same version counter, no grad_fn): holding ``y`` itself would close the
         # cycle ctx -> holder -> y -> grad_fn -> ctx and keep a never-backpropagated tape alive until the cyclic collector runs
         holder["bce_y"], holder["bce_t"] = y.detach(), tgt
         holder["bce_ver"] = (y._version, tgt._version)
         slot.used, slot.loss, slot.holder = True, loss, holder
+    elif lazy is not None:
+        _lib.call("hpri_bn_relu_outconv_fwd", lazy[0].ptr, lazy[0].cs, lazy[0].coff, _p(lazy[1]), _p(lazy[2]), lazy[3], _p(weight),
+                  _p(bias), _p(y), ctypes.c_void_p(0), ctypes.c_void_p(0), 0, x.N, x.H * x.W, C, _stream())
     elif x16:
         _lib.call("hpri_outconv_fwd_x16", *xa, _p(wsrc), _p(bias), _p(y), ctypes.c_void_p(0), ctypes.c_void_p(0), 0,
                   x.N, x.H * x.W, C, K, _stream())
@@ -2364,47 +2497,60 @@ def out_conv(tape: Tape, x: Act, weight: torch.Tensor, bias: Optional[torch.Tens
                         scale_tensors_dev_([gy], tp.gslot, invert=False)
                     else:
                         scale_tensors_([gy], tp.gscale)
-            dw, acc_w = tp.param_slot(weight)
-            db = None
-            if bias is not None:
-                db, _ = tp.param_slot(bias)
-            nblk = ctypes.c_int(); cpart = ctypes.c_int()
-            _lib.call("hpri_outconv_bwd_plan", x.N, x.H * x.W, C, K, ctypes.byref(nblk), ctypes.byref(cpart))
-            ws = _ws(nblk.value * K * 2 * cpart.value, dev)
-            g16 = 0
-            if (need_dx and x16 and K == 1 and x.yr16 and tp.grads.get(id(x)) is None
-                    and (GRAD_BF16_GEMM if k_gap else GRAD_BF16_SINGLE)):
-                # the head is the first writer of this gradient and its readers read bf16: bf16 rows for the last BatchNorm
-                # backward (U-Nets), or for the views of SpectralUNET's last plane concat (tail's half is added to later)
-                gx = tp.grads[id(x)] = _new_grad16(x)
-                gxp, gcs, gco, gcw, acc, g16 = gx.ptr, gx.cs, 0, gx.cw, False, 1
-            elif need_dx:
-                gx, acc = tp.grad_slot(x)
-                gxp, gcs, gco, gcw = gx.ptr, gx.cs, gx.coff, gx.cw
-            else:
-                gxp, gcs, gco, gcw, acc = ctypes.c_void_p(0), 0, 0, 0, False
-            # a gapped weight: its gradient lands in a (K, C) scratch row and moves to the parameter's layout afterwards
-            dwk = torch.empty(K * C, dtype=torch.float32, device=dev) if k_gap else dw
-            dbk = torch.empty(K, dtype=torch.float32, device=dev) if (k_gap and db is not None) else db
-            acc_k = 0 if k_gap else acc_w
-            if x16:
-                _lib.call("hpri_outconv_bwd_x16", _p(gy), _p(tgt) if fused else ctypes.c_void_p(0), _p(gs) if fused else ctypes.c_void_p(0),
-                          *xa, _p(wsrc), gxp, g16, gcs, gco, gcw, int(acc), _p(dwk), _p(dbk), acc_k, _p(ws), ws.numel(),
-                          x.N, x.H * x.W, C, K, _stream())
-            elif fused:
-                _lib.call("hpri_outconv_bwd_bce", _p(gy), _p(tgt), _p(gs), x.ptr, x.cs, x.coff, _p(weight), gxp, gcs, gco, gcw,
-                          int(acc), _p(dw), _p(db), acc_w, _p(ws), ws.numel(), x.N, x.H * x.W, C, K, _stream())
-            else:
-                _lib.call("hpri_outconv_bwd", _p(gy), x.ptr, x.cs, x.coff, _p(weight), gxp, gcs, gco, gcw, int(acc),
-                          _p(dw), _p(db), acc_w, _p(ws), ws.numel(), x.N, x.H * x.W, C, K, _stream())
-            if tp.gscale != 1.0 and fused:
-                _lib.call("hpri_set_loss_scale", 1.0)
-            if k_gap:
-                g0, gl = k_gap
-                _lib.call("hpri_copy_slice_any", _p(dwk), C, 0, _p(dw), Cw, 0, K, g0, 0, acc_w, _stream())
-                _lib.call("hpri_copy_slice_any", _p(dwk), C, g0 + gl, _p(dw), Cw, g0, K, Cw - g0, 0, acc_w, _stream())
-                if db is not None:
-                    _lib.call("hpri_copy_slice_any", _p(dbk), 1, 0, _p(db), 1, 0, K, 1, 0, acc_w, _stream())
+            def classic(tp: Tape) -> None:
+                if x.lazy_bn is not None:
+                    _materialize_bn(x)              # (the two-call route reads the activation: it gets its storage now)
+                dw, acc_w = tp.param_slot(weight)
+                db = None
+                if bias is not None:
+                    db, _ = tp.param_slot(bias)
+                nblk = ctypes.c_int(); cpart = ctypes.c_int()
+                _lib.call("hpri_outconv_bwd_plan", x.N, x.H * x.W, C, K, ctypes.byref(nblk), ctypes.byref(cpart))
+                ws = _ws(nblk.value * K * 2 * cpart.value, dev)
+                g16 = 0
+                if (need_dx and x16 and K == 1 and x.yr16 and tp.grads.get(id(x)) is None
+                        and (GRAD_BF16_GEMM if k_gap else GRAD_BF16_SINGLE)):
+                    # the head is the first writer of this gradient and its readers read bf16: bf16 rows for the last BatchNorm
+                    # backward (U-Nets), or for the views of SpectralUNET's last plane concat (tail's half is added to later)
+                    gx = tp.grads[id(x)] = _new_grad16(x)
+                    gxp, gcs, gco, gcw, acc, g16 = gx.ptr, gx.cs, 0, gx.cw, False, 1
+                elif need_dx:
+                    gx, acc = tp.grad_slot(x)
+                    gxp, gcs, gco, gcw = gx.ptr, gx.cs, gx.coff, gx.cw
+                else:
+                    gxp, gcs, gco, gcw, acc = ctypes.c_void_p(0), 0, 0, 0, False
+                # a gapped weight: its gradient lands in a (K, C) scratch row and moves to the parameter's layout afterwards
+                dwk = torch.empty(K * C, dtype=torch.float32, device=dev) if k_gap else dw
+                dbk = torch.empty(K, dtype=torch.float32, device=dev) if (k_gap and db is not None) else db
+                acc_k = 0 if k_gap else acc_w
+                if x16:
+                    _lib.call("hpri_outconv_bwd_x16", _p(gy), _p(tgt) if fused else ctypes.c_void_p(0), _p(gs) if fused else ctypes.c_void_p(0),
+                              *xa, _p(wsrc), gxp, g16, gcs, gco, gcw, int(acc), _p(dwk), _p(dbk), acc_k, _p(ws), ws.numel(),
+                              x.N, x.H * x.W, C, K, _stream())
+                elif fused:
+                    _lib.call("hpri_outconv_bwd_bce", _p(gy), _p(tgt), _p(gs), x.ptr, x.cs, x.coff, _p(weight), gxp, gcs, gco, gcw,
+                              int(acc), _p(dw), _p(db), acc_w, _p(ws), ws.numel(), x.N, x.H * x.W, C, K, _stream())
+                else:
+                    _lib.call("hpri_outconv_bwd", _p(gy), x.ptr, x.cs, x.coff, _p(weight), gxp, gcs, gco, gcw, int(acc),
+                              _p(dw), _p(db), acc_w, _p(ws), ws.numel(), x.N, x.H * x.W, C, K, _stream())
+                if tp.gscale != 1.0 and fused:
+                    _lib.call("hpri_set_loss_scale", 1.0)
+                if k_gap:
+                    g0, gl = k_gap
+                    _lib.call("hpri_copy_slice_any", _p(dwk), C, 0, _p(dw), Cw, 0, K, g0, 0, acc_w, _stream())
+                    _lib.call("hpri_copy_slice_any", _p(dwk), C, g0 + gl, _p(dw), Cw, g0, K, Cw - g0, 0, acc_w, _stream())
+                    if db is not None:
+                        _lib.call("hpri_copy_slice_any", _p(dbk), 1, 0, _p(db), 1, 0, K, 1, 0, acc_w, _stream())
+            st = tp.bnstage.get(id(x))
+            if (FUSE_HEAD_BN and K == 1 and need_dx and not x16 and not k_gap and st is not None and tp.gscale == 1.0
+                    and id(x) not in tp.grads and id(x) not in tp.headpend and id(x) not in tp.poolpend):
+                # x is the output of a conv -> BN (-> ReLU) stage still to run its backward on this tape and nobody has written a
+                # gradient for it: that stage's BatchNorm backward forms dlogit * w itself and takes the head's dw / db on the
+                # way (_conv_bwd_bn_fused); should another gradient for x turn up before it runs, it calls ``classic``
+                tp.headpend[id(x)] = types.SimpleNamespace(gy=gy, tgt=tgt if fused else None, gs=gs if fused else None, weight=weight,
+                                                           bias=bias, classic=classic)
+                return
+            classic(tp)
         tape.note_params(weight, bias)
         tape.nodes.append(bwd)
     return y, holder

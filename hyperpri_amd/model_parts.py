@@ -26,16 +26,17 @@ def _drain(gen):
         return stop.value
 
 
-def _double_conv_gen(tape, x, seq, train, need_dx=True, precision=None, room=0, out_planes=False, head_next=False):
+def _double_conv_gen(tape, x, seq, train, need_dx=True, precision=None, room=0, out_planes=False, head_next=False, pool_next=False):
     """(conv3x3 -> BN -> ReLU) x 2 on an Act, as a staged program (one stage per convolution); ``seq`` is the 6-entry
     nn.Sequential container.  ``room``: channels to keep free behind the result (it is a skip tensor: the decoder's concat is
     then in place).  ``out_planes``: the result feeds a transposed convolution that reads bf16 planes (bf16 mode): its
-    BatchNorm-apply pass writes them.  ``head_next``: the result is read by the 1x1 output layer only (engine.conv_bn_relu)."""
+    BatchNorm-apply pass writes them.  ``head_next``: the result is read by the 1x1 output layer only (engine.conv_bn_relu).  ``pool_next``: the result is also max-pooled
+    (the next ``Down``): its BatchNorm-apply pass may write the pooled map too."""
     h = E.conv_bn_relu(tape, x, seq[0].weight, seq[0].bias, E.BNRef(seq[1]), train, 3, need_dx=need_dx, precision=precision,
                        next_cout=seq[3].weight.shape[0])       # h is read by the second convolution only
     yield
     return E.conv_bn_relu(tape, h, seq[3].weight, seq[3].bias, E.BNRef(seq[4]), train, 3, precision=precision, room=room,
-                          out_planes=out_planes, head_next=head_next)
+                          out_planes=out_planes, head_next=head_next, pool_next=pool_next)
 
 
 def _double_conv_ops(*args, **kw):
@@ -90,9 +91,9 @@ class DoubleConv(nn.Module):
                   nn.ReLU(inplace=True)]
         self.double_conv = nn.Sequential(*layers)
 
-    def _gen(self, tape, x, need_dx=True, room=0, out_planes=False, head_next=False):
+    def _gen(self, tape, x, need_dx=True, room=0, out_planes=False, head_next=False, pool_next=False):
         return _double_conv_gen(tape, x, self.double_conv, self.training, need_dx, E.precision_of(self), room,
-                                out_planes, head_next)
+                                out_planes, head_next, pool_next)
 
     def _ops(self, *args, **kw):
         return _drain(self._gen(*args, **kw))
@@ -115,8 +116,8 @@ class Down(nn.Module):
         super().__init__()
         self.maxpool_conv = nn.Sequential(nn.MaxPool2d(2), DoubleConv(in_channels, out_channels))
 
-    def _gen(self, tape, x, room=0, out_planes=False):
-        return self.maxpool_conv[1]._gen(tape, E.maxpool2(tape, x), room=room, out_planes=out_planes)
+    def _gen(self, tape, x, room=0, out_planes=False, pool_next=False):
+        return self.maxpool_conv[1]._gen(tape, E.maxpool2(tape, x), room=room, out_planes=out_planes, pool_next=pool_next)
 
     def _ops(self, *args, **kw):
         return _drain(self._gen(*args, **kw))

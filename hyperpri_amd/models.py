@@ -80,13 +80,13 @@ class UNet(nn.Module):
         if self.fused_tape and not has_hooks(self):
             def prog(tape, a, need):
                 # the four skip tensors are produced inside the buffers their concats will use (model_parts.py:87)
-                x1 = yield from self.inc._gen(tape, a[0], need[0], room=skip_room(self.up4))
+                x1 = yield from self.inc._gen(tape, a[0], need[0], room=skip_room(self.up4), pool_next=True)
                 yield
-                x2 = yield from self.down1._gen(tape, x1, room=skip_room(self.up3))
+                x2 = yield from self.down1._gen(tape, x1, room=skip_room(self.up3), pool_next=True)
                 yield
-                x3 = yield from self.down2._gen(tape, x2, room=skip_room(self.up2))
+                x3 = yield from self.down2._gen(tape, x2, room=skip_room(self.up2), pool_next=True)
                 yield
-                x4 = yield from self.down3._gen(tape, x3, room=skip_room(self.up1))
+                x4 = yield from self.down3._gen(tape, x3, room=skip_room(self.up1), pool_next=True)
                 yield
                 # (bf16 mode: what feeds a transposed convolution is also written as planes by its producer)
                 cp = E.convt_planes_mode(self) and not self.bilinear and not self.use_attention
@@ -255,13 +255,13 @@ class CubeNET(torch.nn.Module):
             self.upconv4 = DoubleConv(64 + first_depth, 64)
         self.outc = OutConv(64, self.n_classes)
 
-    def _stem_gen(self, tape, x, need_dx, room=0):
+    def _stem_gen(self, tape, x, need_dx, room=0, pool_next=False):
         prec = E.precision_of(self)
         h = E.conv_bn_relu(tape, x, self.first_conv.weight, self.first_conv.bias, E.BNRef(self.inc[1]),
                            self.training, 3, need_dx=need_dx, precision=prec, next_cout=self.inc2[0].weight.shape[0])
         yield
         return E.conv_bn_relu(tape, h, self.inc2[0].weight, self.inc2[0].bias, E.BNRef(self.inc2[1]),
-                              self.training, 3, precision=prec, room=room)
+                              self.training, 3, precision=prec, room=room, pool_next=pool_next)
 
     def _stem_ops(self, *args, **kw):
         return _drain(self._stem_gen(*args, **kw))
@@ -304,13 +304,13 @@ class CubeNET(torch.nn.Module):
         if self.fused_tape and not has_hooks(self):
             def prog(tape, a, need):
                 up4 = self.up4 if self.first_depth == 64 else self.upsample4
-                x1 = yield from self._stem_gen(tape, a[0], need[0], room=skip_room(up4))
+                x1 = yield from self._stem_gen(tape, a[0], need[0], room=skip_room(up4), pool_next=True)
                 yield
-                x2 = yield from self.down1._gen(tape, x1, room=skip_room(self.up3))
+                x2 = yield from self.down1._gen(tape, x1, room=skip_room(self.up3), pool_next=True)
                 yield
-                x3 = yield from self.down2._gen(tape, x2, room=skip_room(self.up2))
+                x3 = yield from self.down2._gen(tape, x2, room=skip_room(self.up2), pool_next=True)
                 yield
-                x4 = yield from self.down3._gen(tape, x3, room=skip_room(self.up1))
+                x4 = yield from self.down3._gen(tape, x3, room=skip_room(self.up1), pool_next=True)
                 yield
                 cp = E.convt_planes_mode(self) and not self.bilinear and not self.use_attention     # see UNet.forward
                 x5 = yield from self.down4._gen(tape, x4, out_planes=cp)

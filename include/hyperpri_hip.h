@@ -443,6 +443,46 @@ int hpri_outconv_bwd_x16(const float* dy, const float* target, const float* gsca
                          const float* w, void* dx, int dx_bf16, int dx_cs, int dx_coff, int dx_cw, int dx_accumulate, float* dw,
                          float* db, int accumulate_param_grads, float* workspace, size_t ws_floats, int N, long long P, int C, int K,
                          hipStream_t stream);
+/* Sweeps fused with the BatchNorm backward (fp32, one statistics group, C <= 1024).
+ *
+ * hpri_bn_relu_outconv_bwd: backward of  x -> BatchNorm (+ ReLU) -> y -> 1x1 head with one class  in two sweeps of the pre-BN tensor
+ * x: dx (channels [C, Cw) zeros), dgamma / dbeta, dbias (the bias of the convolution in front; as hpri_bn_relu_bwd) and the head's
+ * dw / db.  Neither y nor the head's input gradient is read or written.  `dy` = the logit gradient (N * P values), or -- target !=
+ * NULL -- the logits, with the gradient of the mean BCE-with-logits loss formed inside (gscale, loss scale: hpri_outconv_bwd_bce).
+ * Every result equals hpri_outconv_bwd(_bce) followed by hpri_bn_relu_bwd bit for bit (same per-block partial sums, same finalize
+ * kernels).  workspace: hpri_bn_relu_outconv_bwd_ws floats.
+ *
+ * hpri_bn_relu_bwd_pool: training-mode BatchNorm + ReLU backward of a stage whose output y (N x H x W) feeds MaxPool2d(2) and,
+ * optionally, a skip connection.  The gradient of y arrives as its two terms -- dskip (full resolution; NULL: none) and dpool
+ * (N x H/2 x W/2), routed to the first maximum of each 2x2 window of y as hpri_maxpool2_bwd does -- and is never stored.  dbias is
+ * cleared (exactly zero in training mode) unless accumulate_dbias.  workspace: nblk * 2 * Cpart + 2 * C floats
+ * (hpri_bn_relu_bwd_pool_plan).
+ *
+ * hpri_col_finalize: the second stage of the column reductions by itself: sums[k][c] = sum of `nblk` partial rows [nblk][2][Cpart]
+ * in double, out1 / out2 (optional) (+)= sums[0] / sums[1], zero_out (optional) cleared. */
+/* hpri_bn_relu_outconv_fwd: the forward of the same pair from the pre-BN tensor x (C <= 256): logits and, target != NULL, the fp64 loss
+ * partials, bit for bit those of hpri_bn_apply_relu + hpri_outconv_fwd / hpri_outconv_fwd_bce; y is not stored. */
+int hpri_bn_relu_outconv_fwd(const float* x, int x_cs, int x_coff, const float* scale, const float* shift, int relu, const float* w,
+                             const float* b, float* y, const float* target, double* partial, size_t partial_doubles, int N,
+                             long long P, int C, hipStream_t stream);
+/* hpri_bn_apply_relu_pool: BatchNorm apply (+ ReLU) of a stage whose output is max-pooled next: y (N x H x W) and its MaxPool2d(2) map
+ * (N x H/2 x W/2) in one pass over the pre-BN tensor, both bit-equal to hpri_bn_apply_relu followed by hpri_maxpool2_fwd. */
+int hpri_bn_apply_relu_pool(const float* x, int x_cs, int x_coff, float* y, int y_cs, int y_coff, float* pool, int p_cs, int p_coff,
+                            const float* scale, const float* shift, int N, int H, int W, int C, int Cw, int relu, hipStream_t stream);
+size_t hpri_bn_relu_outconv_bwd_ws(int N, long long P, int C);
+int hpri_bn_relu_outconv_bwd(const float* dy, const float* target, const float* gscale, const float* x, int x_cs, int x_coff,
+                             const float* w, float* dx, int dx_cs, int dx_coff, int Cw, const float* mean, const float* invstd,
+                             const float* scale, const float* shift, float* dgamma, float* dbeta, int accumulate_bn_grads,
+                             float* dbias, int accumulate_dbias, float* dw, float* db, int accumulate_head_grads, float* workspace,
+                             size_t ws_floats, int N, long long P, int C, int relu, int use_batch_stats, hipStream_t stream);
+int hpri_bn_relu_bwd_pool_plan(int N, int H, int W, int C, int* nblk, int* Cpart);
+int hpri_bn_relu_bwd_pool(const float* dskip, int ds_cs, int ds_coff, const float* dpool, int dp_cs, int dp_coff, const float* x,
+                          int x_cs, int x_coff, float* dx, int dx_cs, int dx_coff, const float* mean, const float* invstd,
+                          const float* scale, const float* shift, float* dgamma, float* dbeta, int accumulate_param_grads,
+                          float* dbias, int accumulate_dbias, float* workspace, size_t ws_floats, int N, int H, int W, int C, int Cw,
+                          hipStream_t stream);
+int hpri_col_finalize(const float* part, int nblk, int Cpart, int C, float* sums, float* out1, float* out2, int accumulate,
+                      float* zero_out, hipStream_t stream);
 /* nn.Upsample(scale_factor=2, 'bilinear', align_corners=True) (model_parts.py:57; models.py:195) writing at a pixel
  * offset of a padded destination, its gather-form gradient, and the element-wise "attention" product x2*x1
  * (model_parts.py:84-85). */
