@@ -4,6 +4,7 @@ Drop-in ``torch.nn.Module`` replacements for the reference's ``src/Experiments/m
 ``model_parts.py`` whose forward/backward run in hand-written HIP kernels.  See DESIGN.md.
 """
 from .cache import CubeCache, plan_epoch  # noqa: F401
+from .evaluate import (SplitPrediction, color_segmaps, predict_split, test_net, validate_net, write_segmaps)  # noqa: F401
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)

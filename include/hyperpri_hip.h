@@ -554,6 +554,34 @@ int hpri_cube_gather(const void* cache, int cache_dtype, int slots, int Hs, int 
 int hpri_mask_gather(const unsigned char* masks, int slots, int Hs, int Ws, const int* table, int N, int h, int w,
                      float* dst, hipStream_t stream);
 
+/* ---- colour-coded segmentation maps (segmap.hip; hyperpri_amd/evaluate.py) --------------------------------
+ * The per-pixel arithmetic of eval_color_segmaps (PLTrainer.py:219-267) minus matplotlib: three bands of the image as a
+ * gamma-corrected pseudo-RGB picture (:236-240, `img[hsi_rgb] ** (1 / 2.2)`), prediction and ground truth painted in the
+ * colour-blind palette (:243-258: truth overwrites prediction, agreement overwrites both) and blended over the picture as
+ * `imshow(img); imshow(overlay, alpha=0.6)` blends them (:263-264).  All in fp32, per pixel:
+ *     v_k    = image[n, band_k, y, x]; NaN -> 0; clamped to [0, 1]                       k = R, G, B
+ *     base_k = gamma == 1 ? v_k : powf(v_k, inv_gamma)
+ *     p = is_logits ? 1 / (1 + expf(-pred)) : pred;  s = p > threshold;  g = ((int)mask) != 0     (as hpri_seg_counts decides)
+ *     class  = s + 2 g            0 neither, 1 prediction only, 2 truth only, 3 both
+ *     over   = class ? palette[class - 1] : (0, 0, 0);   out_k = alpha * over_k + (1 - alpha) * base_k
+ *     rgb_k  = (uint8)(out_k * 255 + 0.5f)
+ * The clamp and the NaN rule are this library's; they differ from the reference only where it would hand matplotlib a NaN or
+ * a value outside [0, 1].  The reference's defaults, as data: palette (202,0,32)/255, (5,133,176)/255, (155,191,133)/255;
+ * alpha 0.6 (a pixel of neither class is the picture darkened to 0.4); HSI: bands (125, 49, 0) of the band-sliced cube with
+ * gamma 2.2; RGB images: bands (0, 1, 2), gamma 1.
+ *   image    fp32; element (n, band, y, x) at image[n*sn + band*sc + y*sy + x*sx] (strides in elements, >= 0), C bands: the
+ *            zero-padded channels-last views of the cube cache / stager (sc = 1, sx = cs) and plain (N, C, h, w) alike
+ *   pred, mask  contiguous (N, h, w) fp32;   rgb  (N, h, w, 3) uint8;   classes  (N, h, w) uint8 or NULL
+ *   gamma > 0, inv_gamma = 1 / gamma as the caller forms it (Python: 1 / 2.2, rounded to float once); 0 <= alpha <= 1
+ *   p0* / p1* / p2*  the palette by value: prediction only, truth only, both, each R, G, B in [0, 1]
+ * Argument errors (null pointer, a size <= 0, a band index outside [0, C), gamma <= 0, alpha or a palette entry outside
+ * [0, 1]) are reported before any launch. */
+int hpri_segmap_overlay(const float* image, long long sn, long long sc, long long sy, long long sx, int C, int band_r,
+                        int band_g, int band_b, const float* pred, const float* mask, int N, int h, int w, float threshold,
+                        int is_logits, float gamma, float inv_gamma, float alpha, float p0r, float p0g, float p0b, float p1r,
+                        float p1g, float p1b, float p2r, float p2g, float p2b, unsigned char* rgb, unsigned char* classes,
+                        hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
