@@ -233,7 +233,7 @@ __global__ void bn_apply_relu_kernel(const float* __restrict__ x, int x_cs, int 
 // -------------------------------------------------------------------------------------------------
 // grid = (nblk, ceil(C4/CQ), G); block = 256 = ROWS x CQ; partial layout [G][nblk][2][Cq4*4]
 template <int MODE, bool XB = false, bool DB = false>  // 0: BN+ReLU backward sums (s1 = sum g, s2 = sum g*xhat); 1: plain column sum of dy; DB: dy stored as bf16
-__global__ void col_reduce_kernel(const float* __restrict__ dy, int dy_cs, int dy_coff, const float* __restrict__ x,
+__global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict__ dy, int dy_cs, int dy_coff, const float* __restrict__ x,
                                   int x_cs, int x_coff, const float* __restrict__ mean,
                                   const float* __restrict__ invstd, const float* __restrict__ scale,
                                   const float* __restrict__ shift, long long pix_per_group, int C, int CQ,
@@ -322,12 +322,22 @@ __global__ void col_reduce_kernel(const float* __restrict__ dy, int dy_cs, int d
 }
 
 // stage 2: sums[g][k][c] = sum over blocks (double accumulation, fixed order); k in {0,1}
-__global__ void col_finalize_kernel(const float* __restrict__ part, int nblk, int Cpart, int C, float* __restrict__ sums,
-                                    float* __restrict__ out1, float* __restrict__ out2, int accumulate,
-                                    float* __restrict__ zero_out = nullptr) {
-  __shared__ double s[2][32][32];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl, g = blockIdx.y;
+// Workgroup shape of the two stage-2 kernels: CH channels x 32 row slices = CH * 32 threads, launched with CH = COL_CH = 8 (256
+// threads: one wave per SIMD).  They run on the main stream of the backward while conv_wino_wgrad_kernel (one workgroup per CU,
+// two waves of 192 registers per SIMD, 106 KB of LDS) holds every CU on the side stream; a workgroup of one wave per SIMD fits
+// beside it on any CU, a 1024-thread one (four waves per SIMD) fits on none and waited for a weight-gradient workgroup to retire.
+// The sums do not depend on CH: thread (channel c, slice sl) adds the rows b = sl, sl + 32, ... of its range in ascending order,
+// then one thread per channel adds the 32 slice totals in ascending slice order and rounds once to float.
+constexpr int COL_CH = 8;
+
+template <int CH>
+__global__ __launch_bounds__(CH * 32) void col_finalize_kernel(const float* __restrict__ part, int nblk, int Cpart, int C,
+                                                               float* __restrict__ sums, float* __restrict__ out1,
+                                                               float* __restrict__ out2, int accumulate,
+                                                               float* __restrict__ zero_out = nullptr) {
+  __shared__ double s[2][32][CH];
+  const int cl = threadIdx.x % CH, sl = threadIdx.x / CH;
+  const int c = blockIdx.x * CH + cl, g = blockIdx.y;
   double a1 = 0.0, a2 = 0.0;
   if (c < C) {
     const float* p = part + (size_t)g * nblk * 2 * Cpart + c;
@@ -356,12 +366,14 @@ __global__ void col_finalize_kernel(const float* __restrict__ part, int nblk, in
 }
 
 // Many partial rows (one per tile of a convolution launch that took the reduction in its epilogue: 4.6 k rows for a full-size
-// layer) are first folded to `S` rows by S x C/32 workgroups -- col_finalize_kernel alone walks them with C/32 workgroups.
-// folded[s][k][c] = sum over the rows of slice s (double accumulation, fixed order); grid (ceil(C/32), S), 1024 threads
-__global__ void col_fold_kernel(const float* __restrict__ part, int nblk, int Cpart, int C, float* __restrict__ folded) {
-  __shared__ double s[2][32][32];
-  const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cl;
+// layer) are first folded to `S` rows by S x C/CH workgroups -- col_finalize_kernel alone walks them with C/CH workgroups.
+// folded[s][k][c] = sum over the rows of slice s (double accumulation, fixed order); grid (ceil(C/CH), S), CH * 32 threads
+template <int CH>
+__global__ __launch_bounds__(CH * 32) void col_fold_kernel(const float* __restrict__ part, int nblk, int Cpart, int C,
+                                                           float* __restrict__ folded) {
+  __shared__ double s[2][32][CH];
+  const int cl = threadIdx.x % CH, sl = threadIdx.x / CH;
+  const int c = blockIdx.x * CH + cl;
   const int per = (nblk + gridDim.y - 1) / gridDim.y;
   const int b0 = blockIdx.y * per, b1 = min(b0 + per, nblk);
   double a1 = 0.0, a2 = 0.0;
@@ -401,7 +413,7 @@ __global__ void bn_param_grad_kernel(const float* __restrict__ sums, int G, int 
 // dx = scale * (g - s1/Np - xhat * s2/Np)   (training) ;  dx = scale * g  (eval: use_batch_stats = 0)
 // same 2-D mapping as bn_apply_relu_kernel; also emits per-block column sums of dx (the conv-bias gradient)
 template <bool XB, bool DB = false>
-__global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, int dy_cs, int dy_coff, const float* __restrict__ x,
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, int dy_cs, int dy_coff, const float* __restrict__ x,
                                     int x_cs, int x_coff, float* __restrict__ dx, int dx_cs, int dx_coff,
                                     const float* __restrict__ mean, const float* __restrict__ invstd,
                                     const float* __restrict__ scale, const float* __restrict__ shift,
@@ -661,7 +673,7 @@ static int bn_relu_bwd_impl(const float* ext_part, int ext_nblk, int ext_cpart,
     long long S = ((long long)nblk * 2 * Cpart) / (2ll * ext_cpart);
     if (S > 64) S = 64;
     if (S >= 4 && ext_nblk >= 16 * S) {
-      hipLaunchKernelGGL(col_fold_kernel, dim3(hpri_cdiv(C, 32), (unsigned)S), dim3(1024), 0, stream, ext_part, ext_nblk, ext_cpart, C, part);
+      hipLaunchKernelGGL(col_fold_kernel<COL_CH>, dim3(hpri_cdiv(C, COL_CH), (unsigned)S), dim3(COL_CH * 32), 0, stream, ext_part, ext_nblk, ext_cpart, C, part);
       HPRI_CHECK_LAUNCH();
       fin_part = part; fin_nblk = (int)S;
     }
@@ -685,7 +697,7 @@ static int bn_relu_bwd_impl(const float* ext_part, int ext_nblk, int ext_cpart,
   // all when the caller accumulates).  Eval-mode statistics (use_batch_stats = 0) keep the computed sum: it is not zero there.
   const bool dbias_zero = dbias != nullptr && use_batch_stats;
   float* zero_out = (dbias_zero && !accumulate_dbias && G == 1) ? dbias : nullptr;
-  hipLaunchKernelGGL(col_finalize_kernel, dim3(hpri_cdiv(C, 32), G), dim3(1024), 0, stream, fin_part, fin_nblk, fin_cpart, C, sums,
+  hipLaunchKernelGGL(col_finalize_kernel<COL_CH>, dim3(hpri_cdiv(C, COL_CH), G), dim3(COL_CH * 32), 0, stream, fin_part, fin_nblk, fin_cpart, C, sums,
                      (pg && G == 1) ? dbeta : nullptr, (pg && G == 1) ? dgamma : nullptr, accumulate_param_grads, zero_out);
   HPRI_CHECK_LAUNCH();
   if (dbias_zero && !accumulate_dbias && G > 1) {
@@ -714,7 +726,7 @@ static int bn_relu_bwd_impl(const float* ext_part, int ext_nblk, int ext_cpart,
                        use_batch_stats, dbias != nullptr ? dxpart : nullptr, Cpart, po);
   HPRI_CHECK_LAUNCH();
   if (dbias != nullptr) {
-    hipLaunchKernelGGL(col_finalize_kernel, dim3(hpri_cdiv(C, 32), G), dim3(1024), 0, stream, dxpart, nblk, Cpart, C, dxsums,
+    hipLaunchKernelGGL(col_finalize_kernel<COL_CH>, dim3(hpri_cdiv(C, COL_CH), G), dim3(COL_CH * 32), 0, stream, dxpart, nblk, Cpart, C, dxsums,
                        G == 1 ? dbias : nullptr, (float*)nullptr, accumulate_dbias);
     HPRI_CHECK_LAUNCH();
     if (G > 1) {   // dxsums[g][0][c] = per-group column sums; "dbeta" path of the param-grad kernel adds the groups
@@ -818,7 +830,7 @@ extern "C" int hpri_col_sum(const float* src, int cs, int coff, float* out, int 
                      0, nullptr, nullptr, nullptr, nullptr, P, C, cq, 0, part, Cpart);
   HPRI_CHECK_LAUNCH();
   // sums[0][c] holds the column sums; the finalize kernel writes (or accumulates) them into `out` on the way
-  hipLaunchKernelGGL(col_finalize_kernel, dim3(hpri_cdiv(C, 32), 1), dim3(1024), 0, stream, part, nblk, Cpart, C, sums, out,
+  hipLaunchKernelGGL(col_finalize_kernel<COL_CH>, dim3(hpri_cdiv(C, COL_CH), 1), dim3(COL_CH * 32), 0, stream, part, nblk, Cpart, C, sums, out,
                      (float*)nullptr, accumulate);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;
@@ -830,7 +842,7 @@ extern "C" int hpri_col_sum(const float* src, int cs, int coff, float* out, int 
 extern "C" int hpri_col_finalize(const float* part, int nblk, int Cpart, int C, float* sums, float* out1, float* out2,
                                  int accumulate, float* zero_out, hipStream_t stream) {
   HPRI_REQUIRE(part && sums && nblk > 0 && C > 0 && Cpart >= C, "col_finalize: bad arguments");
-  hipLaunchKernelGGL(col_finalize_kernel, dim3(hpri_cdiv(C, 32), 1), dim3(1024), 0, stream, part, nblk, Cpart, C, sums, out1, out2,
+  hipLaunchKernelGGL(col_finalize_kernel<COL_CH>, dim3(hpri_cdiv(C, COL_CH), 1), dim3(COL_CH * 32), 0, stream, part, nblk, Cpart, C, sums, out1, out2,
                      accumulate, zero_out);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;

@@ -664,15 +664,24 @@ __global__ void wino_wgrad_reduce_kernel(const float* __restrict__ ws, float* __
 }
 
 // The same for MANY slabs (the 608 x 968 layers: 256 slabs of 16 x 64 x 64, 67 MB, which the kernel above reads with 16
-// workgroups): S slab slices x 64 columns per workgroup and ONE input channel; slice s sums slabs s, s + S, ... in order, the
+// workgroups): S slab slices x NC columns per workgroup and ONE input channel; slice s sums slabs s, s + S, ... in order, the
 // slices meet in LDS in order (deterministic).
+// Co-residency: the S = 16 form runs on the side stream while conv_wino4_kernel (two workgroups per CU, one wave of 248
+// registers per SIMD and 78 KB of LDS each) fills the machine on the main stream.  With NC = 32 columns it is a 512-thread
+// workgroup: two waves per SIMD (144 registers) and 30 KB of LDS, which fits on a CU as soon as ONE of the two data-gradient
+// workgroups has left it (264 registers per SIMD and 82 KB free).  As 1024 threads x 64 columns (288 registers per SIMD, 60 KB)
+// it had to wait for both to leave at the same moment.  (A cap of 64 registers per wave on the 1024-thread form spills.)
+// The column count changes which workgroup holds a column, not the order in which its slabs are added.
+constexpr int wino_wide_cols(int S) { return S >= 16 ? 32 : 64; }   // workgroup = S slices x this many columns: 512 threads for S = 8, 16
+
 template <int S>
-__global__ __launch_bounds__(64 * S) void wino_wgrad_reduce_wide_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                                        int splits, int Cr, int Nr, int Cin, int Cout,
-                                                                        int accumulate) {
-  __shared__ float red[S - 1][16][64];
-  const int ln = threadIdx.x & 63, sl = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + ln, c = blockIdx.y;            // n < Nr (a multiple of 64), c < Cin <= Cr
+__global__ __launch_bounds__(wino_wide_cols(S) * S) void wino_wgrad_reduce_wide_kernel(const float* __restrict__ ws,
+                                                                                       float* __restrict__ dw, int splits, int Cr,
+                                                                                       int Nr, int Cin, int Cout, int accumulate) {
+  constexpr int NC = wino_wide_cols(S);
+  __shared__ float red[S - 1][16][NC];
+  const int ln = threadIdx.x % NC, sl = threadIdx.x / NC;
+  const int n = blockIdx.x * NC + ln, c = blockIdx.y;            // n < Nr (a multiple of 64), c < Cin <= Cr
   float u[16];
 #pragma unroll
   for (int xi = 0; xi < 16; ++xi) u[xi] = 0.f;
@@ -774,8 +783,8 @@ extern "C" int hpri_wino_wgrad_reduce(const float* ws, float* dw, int N, int H, 
   int splits, Cr, Nr;
   hpri_wino_wgrad_plan(N, H, W, Cin_pad, Cout_pad, &splits, &Cr, &Nr);
   if (splits >= 64) {                               // many slabs, few (c, n) pairs: spread the slabs over the workgroup too
-    dim3 grid((unsigned)hpri_cdiv(Cout, 64), (unsigned)Cin);
-    hipLaunchKernelGGL(wino_wgrad_reduce_wide_kernel<16>, grid, dim3(1024), 0, stream, ws, dw, splits, Cr, Nr, Cin, Cout, accumulate);
+    dim3 grid((unsigned)hpri_cdiv(Cout, wino_wide_cols(16)), (unsigned)Cin);
+    hipLaunchKernelGGL(wino_wgrad_reduce_wide_kernel<16>, grid, dim3(wino_wide_cols(16) * 16), 0, stream, ws, dw, splits, Cr, Nr, Cin, Cout, accumulate);
   } else if (splits >= 8) {
     dim3 grid((unsigned)hpri_cdiv(Cout, 64), (unsigned)Cin);
     hipLaunchKernelGGL(wino_wgrad_reduce_wide_kernel<8>, grid, dim3(512), 0, stream, ws, dw, splits, Cr, Nr, Cin, Cout, accumulate);

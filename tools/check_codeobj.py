@@ -12,14 +12,20 @@ size to the stated bound.
     python tools/check_codeobj.py            # table of every kernel + verdict
     python tools/check_codeobj.py --json     # the same as one JSON object (tests/test_codeobj.py reads this)
 
+Each row also carries ``max_flat_wg``: the kernel's ``.max_flat_workgroup_size`` from the same metadata (its __launch_bounds__,
+1024 without one) -- with ``vgprs`` and ``lds`` what decides whether a workgroup can be placed on a compute unit beside a resident
+workgroup of another kernel (tests/test_codeobj_coresident.py).
+
 No GPU needed (hipcc cross-compiles).  Results are cached on the source stamp under hyperpri_amd/lib/.
 """
 import hashlib
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,12 +94,43 @@ def _demangle(names):
         return names
 
 
-def analyse(src):
-    cmd = [B._hipcc(), *B.FLAGS, "-x", "hip", "--cuda-device-only", "-c", os.path.join(B.CSRC, src), "-I", B.CSRC,
-           "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+def _readelf():
+    hipcc = shutil.which(B._hipcc()) or B._hipcc()
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    for c in (os.path.join(rocm, "lib", "llvm", "bin", "llvm-readelf"), os.path.join(rocm, "llvm", "bin", "llvm-readelf"),
+              "/opt/rocm/lib/llvm/bin/llvm-readelf", shutil.which("llvm-readelf")):
+        if c and os.path.exists(c):
+            return c
+    raise RuntimeError("llvm-readelf not found")
+
+
+def _max_flat_workgroup_sizes(codeobj):
+    """{mangled kernel name: .max_flat_workgroup_size} from the metadata note of a device code object."""
+    r = subprocess.run([_readelf(), "--notes", codeobj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed on {src}:\n{r.stdout[-4000:]}")
+        raise RuntimeError(f"llvm-readelf failed on {codeobj}:\n{r.stdout[-2000:]}")
+    out, size = {}, None
+    for line in r.stdout.splitlines():          # a kernel's own keys sit at four spaces (its arguments' deeper), sorted by name
+        m = re.match(r"^    \.max_flat_workgroup_size:\s+(\d+)", line)
+        if m:
+            size = int(m.group(1))
+            continue
+        m = re.match(r"^    \.name:\s+(\S+)", line)
+        if m and size is not None:
+            out[m.group(1)] = size
+            size = None
+    return out
+
+
+def analyse(src):
+    with tempfile.TemporaryDirectory() as tmp:
+        co = os.path.join(tmp, src.rsplit(".", 1)[0] + ".co")
+        cmd = [B._hipcc(), *B.FLAGS, "-x", "hip", "--cuda-device-only", "--no-gpu-bundle-output", "-c", os.path.join(B.CSRC, src),
+               "-I", B.CSRC, "-Rpass-analysis=kernel-resource-usage", "-o", co]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed on {src}:\n{r.stdout[-4000:]}")
+        flat = _max_flat_workgroup_sizes(co)
     kernels, cur = [], None
     for line in r.stdout.splitlines():
         m = re.search(r"remark:\s+(.*?):\s+(\S+)\s+\[-Rpass-analysis", line)
@@ -107,6 +144,8 @@ def analyse(src):
             cur[_FIELDS[key]] = int(val)
     for k, d in zip(kernels, _demangle([k["name"] for k in kernels])):
         k["demangled"] = d
+        if k["name"] in flat:                    # (device functions that are no kernels have remarks but no metadata entry)
+            k["max_flat_wg"] = flat[k["name"]]
     return kernels
 
 
