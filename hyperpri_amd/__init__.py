@@ -4,12 +4,14 @@ Drop-in ``torch.nn.Module`` replacements for the reference's ``src/Experiments/m
 ``model_parts.py`` whose forward/backward run in hand-written HIP kernels.  See DESIGN.md.
 """
 from .cache import CubeCache, plan_epoch  # noqa: F401
-from .evaluate import (SplitPrediction, color_segmaps, predict_split, test_net, validate_net, write_segmaps)  # noqa: F401
+from .evaluate import (SplitPrediction, color_classmaps, color_segmaps, default_class_palette, evaluate_multiclass,  # noqa: F401
+                       predict_split, test_net, validate_net, write_segmaps)
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)
-from .trainer import (BCEWithLogitsLoss, forward_loss, FusedAdam, FusedSGD, PRCurve, SegCounts, SegmentationModel,  # noqa: F401
-                      average_precision, load_checkpoint, network_state_dict)
+from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, forward_loss, FusedAdam, FusedSGD, PRCurve, SegConfusion,  # noqa: F401
+                      SegCounts, SegmentationModel, argmax_classes, average_precision, load_checkpoint,
+                      multiclass_metrics_from_confusion, network_state_dict)
 
 __version__ = "0.1.0"
 

@@ -48,11 +48,26 @@ __device__ __forceinline__ float segmap_base(float v, int gamma_is_one, float in
   return gamma_is_one ? v : powf(v, inv_gamma);
 }
 
+__device__ __forceinline__ unsigned segmap_round(float out) { return (unsigned)(out * 255.f + 0.5f); }
+
+__device__ __forceinline__ unsigned segmap_blend(float alpha, float over, float base) {
+  const float out = alpha * over + (1.f - alpha) * base;
+  return segmap_round(out);
+}
+
+// the three bands of `cnt` (compile-time) consecutive pixels of a row, all loads issued before any arithmetic
+template <int CNT>
+__device__ __forceinline__ void segmap_bands(const float* img, const int (&band)[3], long long sc, long long sx, float (&v)[3][CNT]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) v[k][j] = img[band[k] * sc + j * sx];
+}
+
 __device__ __forceinline__ unsigned segmap_level(const SegmapArgs& a, int cls, int k, float base) {
   // (selects, not an indexed read: k is a compile-time constant at every call, the class is per lane)
   const float over = cls == 0 ? 0.f : cls == 1 ? a.palette[k] : cls == 2 ? a.palette[3 + k] : a.palette[6 + k];
-  const float out = a.alpha * over + (1.f - a.alpha) * base;
-  return (unsigned)(out * 255.f + 0.5f);
+  return segmap_blend(a.alpha, over, base);
 }
 
 __global__ __launch_bounds__(SEGMAP_THREADS) void segmap_overlay_kernel(const SegmapArgs a) {
@@ -76,10 +91,7 @@ __global__ __launch_bounds__(SEGMAP_THREADS) void segmap_overlay_kernel(const Se
 #pragma unroll
         for (int j = 0; j < 4; ++j) { x[j] = a.pred[pix + j]; m[j] = a.mask[pix + j]; }
       }
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[k][j] = img[a.band[k] * a.sc + j * a.sx];
+      segmap_bands<4>(img, a.band, a.sc, a.sx, v);
       unsigned char o[12], c[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -153,6 +165,121 @@ extern "C" int hpri_segmap_overlay(const float* image, long long sn, long long s
   const long long cap = 8LL * hpri_cu_count();                      // eight workgroups per CU, grid-stride over the rest
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(segmap_overlay_kernel, dim3((unsigned)blocks), dim3(SEGMAP_THREADS), 0, stream, a);
+  HPRI_CHECK_LAUNCH();
+  return HPRI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The multi-class picture: the same base picture under the colours of a uint8 class map (N, h, w), predicted (hpri_seg_confusion's
+// `classes`) or true.  K colours; class 0 -- the background -- shows the bare picture, and so does a value >= K:
+//   out_k = class == 0 ? base_k : alpha * palette[class][k] + (1 - alpha) * base_k;   rgb_k = (uint8)(out_k * 255 + 0.5f)
+// Same quads, same accesses and the same grid as the overlay above; the palette (at most 64 x 3 floats, by value in the kernel's
+// arguments) is staged in LDS once per workgroup because the class that indexes it differs from lane to lane.
+// ------------------------------------------------------------------------------------------------------------------------
+#define SEGMAP_MAX_CLASSES 64
+
+struct ClassmapArgs {
+  const float* image;
+  long long sn, sc, sy, sx;
+  int band[3];
+  const unsigned char* classes;         // (N, h, w) contiguous
+  int N, h, w, K;
+  int gamma_is_one;
+  float inv_gamma, alpha;
+  unsigned char* rgb;                   // (N, h, w, 3)
+  int vec;                              // classes / rgb allow the 4-byte accesses of an aligned quad
+  float palette[3 * SEGMAP_MAX_CLASSES];
+};
+
+__device__ __forceinline__ unsigned classmap_level(const ClassmapArgs& a, const float* pal, int cls, int k, float base) {
+  return cls == 0 ? segmap_round(base) : segmap_blend(a.alpha, pal[3 * cls + k], base);
+}
+
+__global__ __launch_bounds__(SEGMAP_THREADS) void segmap_classes_kernel(const ClassmapArgs a) {
+  __shared__ float pal[3 * SEGMAP_MAX_CLASSES];
+  for (int i = threadIdx.x; i < 3 * a.K; i += SEGMAP_THREADS) pal[i] = a.palette[i];
+  __syncthreads();
+  const int wq = (a.w + 3) >> 2;
+  const long long items = (long long)a.N * a.h * wq;
+  for (long long it = (long long)blockIdx.x * SEGMAP_THREADS + threadIdx.x; it < items; it += (long long)gridDim.x * SEGMAP_THREADS) {
+    const long long r = it / wq;
+    const int x0 = (int)(it - r * wq) * 4;
+    const long long n = r / a.h;
+    const int y = (int)(r - n * a.h);
+    const long long pix = r * a.w + x0;
+    const float* img = a.image + n * a.sn + y * a.sy + x0 * a.sx;
+    if (x0 + 4 <= a.w) {
+      int c[4];
+      float v[3][4];
+      const bool quad = a.vec && (pix & 3) == 0;
+      if (quad) {
+        const unsigned cw = *reinterpret_cast<const unsigned*>(a.classes + pix);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = (cw >> (8 * j)) & 255u;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = a.classes[pix + j];
+      }
+      segmap_bands<4>(img, a.band, a.sc, a.sx, v);
+      unsigned char o[12];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cls = c[j] < a.K ? c[j] : 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[3 * j + k] = (unsigned char)classmap_level(a, pal, cls, k, segmap_base(v[k][j], a.gamma_is_one, a.inv_gamma));
+      }
+      unsigned char* d = a.rgb + 3 * pix;
+      if (quad) {
+        unsigned* dw = reinterpret_cast<unsigned*>(d);
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          dw[q] = (unsigned)o[4 * q] | ((unsigned)o[4 * q + 1] << 8) | ((unsigned)o[4 * q + 2] << 16) | ((unsigned)o[4 * q + 3] << 24);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) d[q] = o[q];
+      }
+    } else {
+      for (int j = 0; x0 + j < a.w; ++j) {
+        float v[3][1];
+        segmap_bands<1>(img + j * a.sx, a.band, a.sc, a.sx, v);
+        const int cj = a.classes[pix + j], cls = cj < a.K ? cj : 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          a.rgb[3 * (pix + j) + k] = (unsigned char)classmap_level(a, pal, cls, k, segmap_base(v[k][0], a.gamma_is_one, a.inv_gamma));
+      }
+    }
+  }
+}
+
+// image, strides, C, bands, gamma / inv_gamma, alpha: as hpri_segmap_overlay.  classes: contiguous (N, h, w) uint8.
+// palette: K x 3 HOST floats in [0, 1] (row 0 is never shown), 2 <= K <= 64.  rgb: (N, h, w, 3) uint8.
+extern "C" int hpri_segmap_classes(const float* image, long long sn, long long sc, long long sy, long long sx, int C, int band_r,
+                                   int band_g, int band_b, const unsigned char* classes, int N, int h, int w, float gamma,
+                                   float inv_gamma, float alpha, const float* palette, int K, unsigned char* rgb,
+                                   hipStream_t stream) {
+  HPRI_REQUIRE(image && classes && palette && rgb, "segmap_classes: null pointer");
+  HPRI_REQUIRE(K >= 2 && K <= SEGMAP_MAX_CLASSES, "segmap_classes: the number of classes must lie in [2, 64]");
+  HPRI_REQUIRE(N > 0 && h > 0 && w > 0 && C > 0, "segmap_classes: bad sizes");
+  HPRI_REQUIRE(sn >= 0 && sc >= 0 && sy >= 0 && sx >= 0, "segmap_classes: negative stride");
+  HPRI_REQUIRE(band_r >= 0 && band_r < C && band_g >= 0 && band_g < C && band_b >= 0 && band_b < C,
+               "segmap_classes: band index outside [0, C)");
+  HPRI_REQUIRE(gamma > 0.f && inv_gamma > 0.f, "segmap_classes: gamma must be positive");
+  HPRI_REQUIRE(alpha >= 0.f && alpha <= 1.f, "segmap_classes: alpha must lie in [0, 1]");
+  ClassmapArgs a;
+  for (int i = 0; i < 3 * SEGMAP_MAX_CLASSES; ++i) {
+    if (i < 3 * K) HPRI_REQUIRE(palette[i] >= 0.f && palette[i] <= 1.f, "segmap_classes: palette entries must lie in [0, 1]");
+    a.palette[i] = i < 3 * K ? palette[i] : 0.f;
+  }
+  a.image = image; a.sn = sn; a.sc = sc; a.sy = sy; a.sx = sx;
+  a.band[0] = band_r; a.band[1] = band_g; a.band[2] = band_b;
+  a.classes = classes; a.N = N; a.h = h; a.w = w; a.K = K;
+  a.gamma_is_one = gamma == 1.f; a.inv_gamma = inv_gamma; a.alpha = alpha; a.rgb = rgb;
+  a.vec = (((uintptr_t)classes | (uintptr_t)rgb) & 3) == 0;
+  const long long items = (long long)N * h * ((w + 3) / 4);
+  long long blocks = (items + SEGMAP_THREADS - 1) / SEGMAP_THREADS;
+  const long long cap = 8LL * hpri_cu_count();
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(segmap_classes_kernel, dim3((unsigned)blocks), dim3(SEGMAP_THREADS), 0, stream, a);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;
 }

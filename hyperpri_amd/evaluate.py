@@ -28,7 +28,8 @@ from torch import nn
 
 from . import _lib
 from .engine import _p, _require_cuda, _stream
-from .trainer import PRCurve, SegCounts, average_precision, best_dice_threshold
+from .trainer import (MAX_CLASSES, PRCurve, SegCounts, _TARGET_KIND, _class_logits, _class_target, _confusion_pass, _ignore_args,
+                      _split_counts, average_precision, best_dice_threshold, multiclass_metrics_from_confusion)
 
 # eval_color_segmaps, restated as data: the colour-blind palette (PLTrainer.py:255-258: prediction only, truth only, both), the
 # overlay's alpha (:264), the bands shown as R (700 nm), G (546 nm), B (436 nm) of the band-sliced cube and its gamma (:238-239)
@@ -244,16 +245,23 @@ def color_segmaps(image: torch.Tensor, logits: torch.Tensor, mask: torch.Tensor,
     return (rgb, classes) if return_classes else rgb
 
 
+def _write_picture(stem: str, rgb: np.ndarray) -> str:
+    """One uint8 (h, w, 3) picture -> ``<stem>.png`` with PIL when PIL is importable, ``<stem>.npy`` otherwise; returns the path."""
+    try:
+        from PIL import Image
+    except ImportError:
+        np.save(stem + ".npy", rgb)
+        return stem + ".npy"
+    Image.fromarray(rgb).save(stem + ".png")
+    return stem + ".png"
+
+
 def write_segmaps(directory: str, split_pred: SplitPrediction, batches: Iterable[dict], threshold: float, **overlay) -> List[str]:
     """The second pass of ``validate_net(save_segmaps=True)`` / ``test_net(save_segmaps=True)`` (PLTrainer.py:602-606, 622) without
     running the network again: ``batches`` serves the split once more in the order ``predict_split`` saw it, each batch's
     images are paired with the stored logits and masks and rendered by ``color_segmaps`` (``overlay``: its ``bands``, ``gamma``,
     ``alpha``, ``palette``), and 3 bytes per pixel go to the host.  Writes ``<name>_seg.png`` with PIL when PIL is importable,
     ``<name>_seg.npy`` (uint8 (h, w, 3)) otherwise; returns the paths."""
-    try:
-        from PIL import Image
-    except ImportError:
-        Image = None
     os.makedirs(directory, exist_ok=True)
     paths: List[str] = []
     i = 0
@@ -269,14 +277,155 @@ def write_segmaps(directory: str, split_pred: SplitPrediction, batches: Iterable
         a, b = split_pred.offsets[i], split_pred.offsets[i + n]
         rgb = color_segmaps(image, split_pred.logits[a:b], split_pred.masks[a:b], threshold, **overlay).cpu().numpy()
         for j in range(n):
-            stem = os.path.join(directory, f"{split_pred.names[i + j]}_seg")
-            if Image is not None:
-                Image.fromarray(rgb[j]).save(stem + ".png")
-                paths.append(stem + ".png")
-            else:
-                np.save(stem + ".npy", rgb[j])
-                paths.append(stem + ".npy")
+            paths.append(_write_picture(os.path.join(directory, f"{split_pred.names[i + j]}_seg"), rgb[j]))
         i += n
     if i != len(split_pred):
         raise ValueError(f"write_segmaps: the batches held {i} of the {len(split_pred)} stored images")
     return paths
+
+
+# ---------------------------------------------------------------------------------------------------
+# The multi-class counterparts (csrc/multiclass.hip, hpri_segmap_classes): one pass over a split, nothing stored
+# ---------------------------------------------------------------------------------------------------
+# Colour-blind-safe colours (the three of PALETTE, then the rest of the Okabe-Ito set) for the first classes above the background
+_CLASS_COLOURS = (*PALETTE, (230 / 255, 159 / 255, 0.0), (86 / 255, 180 / 255, 233 / 255), (0.0, 158 / 255, 115 / 255),
+                  (240 / 255, 228 / 255, 66 / 255), (0.0, 114 / 255, 178 / 255), (213 / 255, 94 / 255, 0.0), (204 / 255, 121 / 255, 167 / 255))
+
+
+def default_class_palette(num_classes: int) -> Tuple[Tuple[float, float, float], ...]:
+    """``num_classes`` rows of R, G, B in [0, 1]: row 0 belongs to the background, which shows the bare picture, so it is never
+    used (black); rows 1.. are distinct colours -- the colour-blind palette of ``color_segmaps`` first, golden-ratio hues at three
+    brightness levels beyond the tenth."""
+    import colorsys
+    rows = [(0.0, 0.0, 0.0), *_CLASS_COLOURS[:max(0, num_classes - 1)]]
+    i = 0
+    while len(rows) < num_classes:
+        rows.append(colorsys.hsv_to_rgb((0.11 + i * 0.6180339887) % 1.0, 0.85 if i % 2 else 0.55, (1.0, 0.8, 0.6)[(i // 2) % 3]))
+        i += 1
+    return tuple(rows)
+
+
+def _image4d(image: torch.Tensor, who: str) -> torch.Tensor:
+    if image.dim() == 5:                # CubeNET cube (N,1,C,h,w) -> (N,C,h,w), as autograd._as4d
+        if image.shape[1] != 1:
+            raise RuntimeError("hyperpri_amd: 5-D input must be (N,1,D,H,W)")
+        image = image.reshape(image.shape[0], image.shape[2], image.shape[3], image.shape[4])
+    if image.dim() != 4:
+        raise ValueError(f"{who}: need a (N,C,h,w) image or a (N,1,C,h,w) cube, got {tuple(image.shape)}")
+    return image
+
+
+def color_classmaps(image: torch.Tensor, classes: torch.Tensor, palette: Optional[Sequence[Sequence[float]]] = None,
+                    alpha: float = ALPHA, bands: Optional[Sequence[int]] = None, gamma: Optional[float] = None) -> torch.Tensor:
+    """The multi-class picture (``hpri_segmap_classes``): the device uint8 (N, h, w, 3) picture of ``image``'s three ``bands``,
+    gamma-corrected exactly as ``color_segmaps`` shows them, with every pixel of a class above 0 blended with that class's colour
+    at ``alpha``; class 0 -- and any value not below the palette's length -- shows the bare picture.
+
+    ``classes``: a uint8 class map (N, h, w) or (N, 1, h, w), predicted (``argmax_classes``) or true; other dtypes are converted.
+    ``palette``: K rows of R, G, B in [0, 1], 2 <= K <= 64, row 0 unused (default: ``default_class_palette(64)``, a colour for
+    every class the kernels support).  ``image``, ``bands`` and ``gamma``: as ``color_segmaps``."""
+    _require_cuda(image, "class-map image")
+    _require_device(classes, "class map")
+    image = _image4d(image, "color_classmaps")
+    N, C, h, w = (int(s) for s in image.shape)
+    if classes.numel() != N * h * w:
+        raise ValueError(f"color_classmaps: need a {N}x{h}x{w} class map, got {tuple(classes.shape)}")
+    if bands is None:
+        bands = HSI_BANDS if C > 3 else RGB_BANDS
+    if gamma is None:
+        gamma = HSI_GAMMA if C > 3 else RGB_GAMMA
+    bands = [int(b) for b in bands]
+    rows = default_class_palette(MAX_CLASSES) if palette is None else [tuple(float(v) for v in colour) for colour in palette]
+    if len(bands) != 3 or any(len(r) != 3 for r in rows) or not 2 <= len(rows) <= MAX_CLASSES:
+        raise ValueError(f"color_classmaps: need three band indices and a palette of 2..{MAX_CLASSES} R, G, B colours")
+    import ctypes
+    pal = (ctypes.c_float * (3 * len(rows)))(*[v for r in rows for v in r])
+    gamma = float(gamma)
+    with torch.cuda.device(image.device):
+        cls = (classes if classes.dtype == torch.uint8 else classes.to(torch.uint8)).reshape(N, h, w).contiguous()
+        rgb = torch.empty((N, h, w, 3), dtype=torch.uint8, device=image.device)
+        sn, sc, sy, sx = image.stride()
+        _lib.call("hpri_segmap_classes", _p(image), sn, sc, sy, sx, C, bands[0], bands[1], bands[2], _p(cls), N, h, w, gamma,
+                  1.0 / gamma if gamma > 0 else 0.0, float(alpha), ctypes.cast(pal, ctypes.c_void_p), len(rows), _p(rgb), _stream())
+    return rgb
+
+
+def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes: int, ignore_index: Optional[int] = None,
+                        class_weight: Optional[torch.Tensor] = None, segmap_dir: Optional[str] = None,
+                        palette: Optional[Sequence[Sequence[float]]] = None, alpha: float = ALPHA,
+                        bands: Optional[Sequence[int]] = None, gamma: Optional[float] = None) -> Dict[str, object]:
+    """A split under a multi-class network in ONE pass, with ``predict_split``'s contract (``eval()`` under
+    ``torch.inference_mode()``, the previous mode restored, ``{'image', 'mask', 'index'}`` batches with device tensors, ragged
+    batches and images of different sizes fine) -- but the (N, K, h, w) logits are never stored.  Per batch, on the device:
+
+    * the confusion matrix of ``argmax(logits, 1)`` against the mask's class indices accumulates (``hpri_seg_confusion``);
+    * the sum-reduced cross-entropy and its divisor -- the ``class_weight`` sum over the pixels that count -- accumulate in fp64
+      (``hpri_softmax_ce_fwd``);
+    * with ``segmap_dir``, the predicted class map of the same pass is rendered by ``color_classmaps`` (``palette``, default
+      ``default_class_palette(num_classes)``; ``alpha``, ``bands``, ``gamma``) and written as ``<name>_seg.png`` (``.npy`` without
+      PIL) -- 3 bytes per pixel go to the host.
+
+    One host synchronisation at the end.  Returns ``ce_loss`` (what ``nn.CrossEntropyLoss(class_weight, ignore_index)`` gives over
+    all pixels of the split), the entries of ``multiclass_metrics_from_confusion``, ``names`` and, with ``segmap_dir``, ``paths``.
+    Raises ``ValueError`` if a mask held a value outside [0, num_classes) that was not ``ignore_index``."""
+    K = int(num_classes)
+    if not 2 <= K <= MAX_CLASSES:
+        raise ValueError(f"evaluate_multiclass: the number of classes must lie in [2, {MAX_CLASSES}], got {num_classes}")
+    if segmap_dir is not None:
+        os.makedirs(segmap_dir, exist_ok=True)
+        if palette is None:
+            palette = default_class_palette(K)
+    was_training = network.training
+    names: List[object] = []
+    paths: List[str] = []
+    counts = totals = weight = None
+    use_ignore, ignore = _ignore_args(ignore_index)
+    network.eval()
+    try:
+        with torch.inference_mode():
+            for batch in batches:
+                image, mask = batch["image"], batch["mask"]
+                _require_cuda(image, "evaluation image")
+                _require_device(mask, "evaluation mask")
+                pred = network(image)
+                if isinstance(pred, tuple):                  # analyze=True networks return (pred, features)
+                    pred = pred[0]
+                if pred.dim() != 4 or int(pred.shape[1]) != K:
+                    raise ValueError(f"evaluate_multiclass: need (N, {K}, h, w) logits, got {tuple(pred.shape)}")
+                x = _class_logits(pred.detach().to(torch.float32), "evaluation logits")
+                n, _, h, w = (int(v) for v in x.shape)
+                batch_names = _names(batch.get("index"), n)
+                with torch.cuda.device(x.device):
+                    t = _class_target(mask, x, "evaluation mask")
+                    if counts is None:
+                        counts = torch.zeros(K * K + 1, dtype=torch.int64, device=x.device)
+                        totals = torch.zeros(3, dtype=torch.float64, device=x.device)
+                        if class_weight is not None:
+                            if tuple(class_weight.shape) != (K,):
+                                raise ValueError(f"evaluate_multiclass: class_weight must have shape ({K},), got {tuple(class_weight.shape)}")
+                            weight = class_weight.detach().to(device=x.device, dtype=torch.float32).contiguous()
+                    classes = torch.empty((n, h, w), dtype=torch.uint8, device=x.device) if segmap_dir is not None else None
+                    _confusion_pass(x, t, ignore_index, counts, classes)
+                    nws = _lib.load().hpri_softmax_ce_workspace_doubles(n * h * w)
+                    ws = torch.empty(nws, dtype=torch.float64, device=x.device)
+                    lse = torch.empty((n, h * w), dtype=torch.float32, device=x.device)
+                    scalars = torch.empty(2, dtype=torch.float32, device=x.device)
+                    _lib.call("hpri_softmax_ce_fwd", _p(x), _p(t), _TARGET_KIND[t.dtype], _p(weight), n, K, h * w, use_ignore, ignore,
+                              0, _p(scalars[0]), _p(lse), _p(scalars[1]), _p(totals), _p(ws), nws, _stream())
+                if segmap_dir is not None:
+                    rgb = color_classmaps(image, classes, palette=palette, alpha=alpha, bands=bands, gamma=gamma).cpu().numpy()
+                    for j in range(n):
+                        paths.append(_write_picture(os.path.join(segmap_dir, f"{batch_names[j]}_seg"), rgb[j]))
+                names.extend(batch_names)
+            if counts is None:
+                raise ValueError("evaluate_multiclass: no batches")
+            matrix = _split_counts(counts.tolist(), K)      # the host synchronisation
+            loss_sum, weight_sum, _ = totals.tolist()
+    finally:
+        network.train(was_training)
+    out: Dict[str, object] = {"ce_loss": loss_sum / weight_sum if weight_sum > 0 else float("nan")}
+    out.update(multiclass_metrics_from_confusion(matrix))
+    out["names"] = names
+    if segmap_dir is not None:
+        out["paths"] = paths
+    return out

@@ -200,6 +200,222 @@ def metrics_from_counts(tp: float, fp: float, fn: float, tn: float) -> Dict[str,
 
 
 # ---------------------------------------------------------------------------------------------------
+# The multi-class tail (csrc/multiclass.hip): nn.CrossEntropyLoss, argmax + confusion matrix, the metrics it reduces to
+# ---------------------------------------------------------------------------------------------------
+MAX_CLASSES = 64
+_TARGET_KIND = {torch.float32: 0, torch.uint8: 1, torch.int64: 2}      # hpri_softmax_ce_fwd / hpri_seg_confusion: target_kind
+
+
+def _class_logits(pred: torch.Tensor, what: str) -> torch.Tensor:
+    _require_cuda(pred, what)
+    if pred.dim() != 4:
+        raise ValueError(f"{what}: need (N, K, h, w) logits, got {tuple(pred.shape)}")
+    if not 2 <= int(pred.shape[1]) <= MAX_CLASSES:
+        raise ValueError(f"{what}: the number of classes must lie in [2, {MAX_CLASSES}], got {int(pred.shape[1])}")
+    return pred if pred.is_contiguous() else pred.contiguous()
+
+
+def _class_target(target: torch.Tensor, x: torch.Tensor, what: str) -> torch.Tensor:
+    """(N, h, w) or (N, 1, h, w) class indices -> contiguous fp32 / uint8 / int64 on the logits' device (other integer types
+    become int64, other floating types fp32)."""
+    if not target.is_cuda:
+        raise RuntimeError(f"hyperpri_amd: {what} is on {target.device}; the hot path exists only as HIP kernels for MI355X "
+                           "(no CPU fallback). Move the module and its inputs to a ROCm device.")
+    N, _, h, w = x.shape
+    if tuple(target.shape) not in ((N, h, w), (N, 1, h, w)):
+        raise ValueError(f"{what}: expected a target of shape {(N, h, w)} or {(N, 1, h, w)} for logits {tuple(x.shape)}, got "
+                         f"{tuple(target.shape)}")
+    if target.dtype not in _TARGET_KIND:
+        target = target.to(torch.float32 if target.is_floating_point() else torch.int64)
+    return target if target.is_contiguous() else target.contiguous()
+
+
+def _ignore_args(ignore_index: Optional[int]) -> Tuple[int, int]:
+    return (0, 0) if ignore_index is None else (1, int(ignore_index))
+
+
+class _CEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor], ignore_index: Optional[int], mean: bool):
+        x = _class_logits(pred, "CrossEntropyLoss input")
+        with torch.cuda.device(x.device):
+            t = _class_target(target, x, "CrossEntropyLoss target")
+            N, K, h, w = (int(v) for v in x.shape)
+            if weight is not None:
+                _require_cuda(weight, "CrossEntropyLoss weight")
+                if tuple(weight.shape) != (K,):
+                    raise ValueError(f"CrossEntropyLoss: weight must have shape ({K},), got {tuple(weight.shape)}")
+                weight = weight.contiguous()
+            use_ignore, ignore = _ignore_args(ignore_index)
+            nws = _lib.load().hpri_softmax_ce_workspace_doubles(N * h * w)
+            ws = torch.empty(nws, dtype=torch.float64, device=x.device)
+            lse = torch.empty((N, h * w), dtype=torch.float32, device=x.device)
+            loss = torch.empty((), dtype=torch.float32, device=x.device)
+            denom = torch.empty((), dtype=torch.float32, device=x.device)
+            _lib.call("hpri_softmax_ce_fwd", _p(x), _p(t), _TARGET_KIND[t.dtype], _p(weight), N, K, h * w, use_ignore, ignore,
+                      int(mean), _p(loss), _p(lse), _p(denom), None, _p(ws), nws, _stream())
+            ctx.save_for_backward(x, lse, t, denom, *(() if weight is None else (weight,)))
+            ctx.ignore, ctx.shape = (use_ignore, ignore), pred.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout: torch.Tensor):
+        x, lse, t, denom, *rest = ctx.saved_tensors
+        weight = rest[0] if rest else None
+        with torch.cuda.device(x.device):
+            g = gout.contiguous().to(torch.float32)
+            N, K, h, w = (int(v) for v in x.shape)
+            dx = torch.empty_like(x)
+            _lib.call("hpri_softmax_ce_bwd", _p(x), _p(lse), _p(t), _TARGET_KIND[t.dtype], _p(weight), N, K, h * w, *ctx.ignore,
+                      _p(denom), _p(g), _p(dx), _stream())
+        return dx.view(ctx.shape), None, None, None, None
+
+
+class CrossEntropyLoss(nn.Module):
+    """``nn.CrossEntropyLoss(weight, ignore_index, reduction)`` over (N, K, h, w) fp32 logits, 2 <= K <= 64, and one class index per
+    pixel -- (N, h, w) or (N, 1, h, w), fp32 holding integers (what ``CubeCache`` emits), uint8 or int64; other integer types are
+    converted.  One pass forward (log-sum-exp per pixel, fp64 partial sums in a fixed order -> bit-reproducible), one pass
+    backward.  ``reduction``: "mean" (the loss sum over the weight sum of the pixels that count, as torch) or "sum".
+
+    A target outside [0, K) that is not ``ignore_index`` cannot raise without a host synchronisation: it makes the loss NaN
+    (and leaves zeros in that pixel's gradient) instead of faulting.  An all-ignored "mean" batch is NaN, as in torch."""
+
+    def __init__(self, weight: Optional[torch.Tensor] = None, ignore_index: Optional[int] = -100, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"CrossEntropyLoss: reduction must be 'mean' or 'sum', got {reduction!r}")
+        if weight is not None and weight.dim() != 1:
+            raise ValueError(f"CrossEntropyLoss: weight must be a (K,) tensor, got {tuple(weight.shape)}")
+        self.register_buffer("weight", None if weight is None else weight.detach().to(torch.float32).clone())
+        self.ignore_index = ignore_index
+        self.reduction = reduction
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:   # noqa: A002 (torch's names)
+        return _CEFn.apply(input, target, self.weight, self.ignore_index, self.reduction == "mean")
+
+
+def _confusion_pass(logits: torch.Tensor, target: Optional[torch.Tensor], ignore_index: Optional[int],
+                    counts: Optional[torch.Tensor], classes: Optional[torch.Tensor]) -> None:
+    """One ``hpri_seg_confusion`` launch on prepared tensors (``_class_logits`` / ``_class_target``)."""
+    N, K, h, w = (int(v) for v in logits.shape)
+    use_ignore, ignore = _ignore_args(ignore_index)
+    _lib.call("hpri_seg_confusion", _p(logits), _p(target), 0 if target is None else _TARGET_KIND[target.dtype], N, K, h * w,
+              use_ignore, ignore, _p(counts), _p(classes), _stream())
+
+
+def argmax_classes(logits: torch.Tensor) -> torch.Tensor:
+    """``torch.argmax(logits, 1)`` of (N, K, h, w) fp32 logits as a uint8 class map (N, h, w): the lowest index among equal maxima,
+    a NaN counts as the maximum."""
+    x = _class_logits(logits.detach(), "argmax_classes input")
+    with torch.cuda.device(x.device):
+        classes = torch.empty((x.shape[0], x.shape[2], x.shape[3]), dtype=torch.uint8, device=x.device)
+        _confusion_pass(x, None, None, None, classes)
+    return classes
+
+
+def multiclass_metrics_from_confusion(matrix) -> Dict[str, object]:
+    """Metrics of a K x K confusion matrix C[truth][prediction] (anything ``numpy.asarray`` takes), on the host:
+
+    * ``acc`` = trace / total;
+    * per class, from its row sum (truth), column sum (prediction) and diagonal entry: ``iou_per_class`` = C_cc / (row + col - C_cc),
+      ``dice_per_class`` = 2 C_cc / (row + col); a class with a zero denominator -- absent from truth and prediction -- is ``nan``;
+    * ``mean_iou`` / ``mean_dice``: the mean over the classes that are not ``nan`` (``nan`` when none is left);
+    * ``confusion``: the matrix itself (int64 numpy array).
+
+    These definitions are this project's own."""
+    import numpy as np
+    c = np.asarray(matrix.cpu() if isinstance(matrix, torch.Tensor) else matrix).astype(np.int64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise ValueError(f"multiclass_metrics_from_confusion: need a square matrix, got shape {c.shape}")
+    nan = float("nan")
+    diag = [int(v) for v in np.diag(c)]
+    both = [int(r) + int(k) for r, k in zip(c.sum(axis=1), c.sum(axis=0))]
+    total = int(c.sum())
+    iou = [d / (b - d) if b - d > 0 else nan for d, b in zip(diag, both)]
+    dice = [2 * d / b if b > 0 else nan for d, b in zip(diag, both)]
+
+    def mean(vals):
+        kept = [v for v in vals if v == v]
+        return sum(kept) / len(kept) if kept else nan
+    return {"acc": sum(diag) / total if total > 0 else nan, "iou_per_class": iou, "dice_per_class": dice,
+            "mean_iou": mean(iou), "mean_dice": mean(dice), "confusion": c}
+
+
+def _split_counts(row: List[int], K: int):
+    """A K*K + 1 count row -> the K x K matrix; raises if the row's invalid-target counter is set."""
+    if row[K * K]:
+        raise ValueError(f"{row[K * K]} target values were neither inside [0, {K}) nor the ignore_index")
+    return [row[i * K:(i + 1) * K] for i in range(K)]
+
+
+class SegConfusion:
+    """The K x K confusion matrix of ``argmax(logits, 1)`` against a class-index target, accumulated on the device
+    (int64, ``counts[t*K + p]``; one more entry counts invalid targets).  ``compute()`` is the one host synchronisation: it raises
+    ``ValueError`` if any target was neither inside [0, K) nor ``ignore_index``, and returns ``multiclass_metrics_from_confusion``."""
+
+    def __init__(self, num_classes: int, ignore_index: Optional[int] = None, device=None):
+        self.num_classes = int(num_classes)
+        if not 2 <= self.num_classes <= MAX_CLASSES:
+            raise ValueError(f"SegConfusion: the number of classes must lie in [2, {MAX_CLASSES}], got {num_classes}")
+        self.ignore_index = ignore_index
+        self.counts = None if device is None else torch.zeros(self.num_classes ** 2 + 1, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        if self.counts is not None:
+            self.counts.zero_()
+
+    def update(self, logits: torch.Tensor, target: torch.Tensor, classes: Optional[torch.Tensor] = None) -> None:
+        """``classes``: optional uint8 (N, h, w) tensor that receives the predicted class map in the same pass."""
+        x = _class_logits(logits.detach(), "SegConfusion prediction")
+        if int(x.shape[1]) != self.num_classes:
+            raise ValueError(f"SegConfusion: built for {self.num_classes} classes, got logits {tuple(x.shape)}")
+        with torch.cuda.device(x.device):
+            t = _class_target(target, x, "SegConfusion target")
+            if self.counts is None:
+                self.counts = torch.zeros(self.num_classes ** 2 + 1, dtype=torch.int64, device=x.device)
+            _confusion_pass(x, t, self.ignore_index, self.counts, classes)
+
+    def matrix(self) -> List[List[int]]:
+        if self.counts is None:
+            raise ValueError("SegConfusion: no update yet")
+        return _split_counts(self.counts.tolist(), self.num_classes)      # the one host synchronisation
+
+    def compute(self) -> Dict[str, object]:
+        return multiclass_metrics_from_confusion(self.matrix())
+
+
+class _StepConfusion:
+    """One K*K + 1 count row per step, kept on the device like ``_StepCounts``."""
+
+    def __init__(self, num_classes: int, ignore_index: Optional[int], device, capacity: int = 256):
+        self.K, self.ignore_index = int(num_classes), ignore_index
+        self.buf = torch.zeros((capacity, self.K ** 2 + 1), dtype=torch.int64, device=device)
+        self.weights: List[int] = []
+        self.n = 0
+
+    def reset(self) -> None:
+        self.buf.zero_()
+        self.weights.clear()
+        self.n = 0
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        x = _class_logits(pred.detach(), "prediction")
+        if int(x.shape[1]) != self.K:
+            raise ValueError(f"SegmentationModel: built for {self.K} classes, got logits {tuple(x.shape)}")
+        with torch.cuda.device(x.device):
+            if self.n == self.buf.shape[0]:
+                grown = torch.zeros((2 * self.n, self.buf.shape[1]), dtype=torch.int64, device=self.buf.device)
+                grown[:self.n].copy_(self.buf)
+                self.buf = grown
+            _confusion_pass(x, _class_target(target, x, "mask"), self.ignore_index, self.buf[self.n], None)
+            self.weights.append(int(pred.shape[0]))
+            self.n += 1
+
+    def rows(self) -> Tuple[List[List[int]], List[int]]:
+        return self.buf[:self.n].tolist(), list(self.weights)
+
+
+# ---------------------------------------------------------------------------------------------------
 # PrecisionRecallCurve('binary', thresholds=500) and the best-Dice threshold (PLTrainer.py:542-556)
 # ---------------------------------------------------------------------------------------------------
 class PRCurve:
@@ -390,10 +606,18 @@ class SegmentationModel(nn.Module):
     ``epoch_metrics`` (the ``on_epoch=True`` logging of the reference)."""
 
     def __init__(self, network: nn.Module, criterion: Optional[nn.Module] = None, optimizer: str = "Adam",
-                 lr: float = 1e-3, weight_decay: float = 0.0, momentum: float = 0.9, threshold: float = 0.5):
+                 lr: float = 1e-3, weight_decay: float = 0.0, momentum: float = 0.9, threshold: float = 0.5,
+                 task: str = "binary", num_classes: int = 1):
         super().__init__()
+        if task not in ("binary", "multiclass"):
+            raise ValueError(f"SegmentationModel: task must be 'binary' or 'multiclass', got {task!r}")
+        if task == "multiclass" and not 2 <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"SegmentationModel: a multiclass task needs 2 <= num_classes <= {MAX_CLASSES}, got {num_classes}")
+        self.task, self.num_classes = task, int(num_classes)
         self.m_network = network
-        self.f_criterion = criterion if criterion is not None else BCEWithLogitsLoss()
+        if criterion is None:
+            criterion = BCEWithLogitsLoss() if task == "binary" else CrossEntropyLoss()
+        self.f_criterion = criterion
         self.p_optimizer, self.p_learn_rate, self.p_decay, self.p_momentum = optimizer, lr, weight_decay, momentum
         self.threshold = threshold
         self.predict_labels: List[torch.Tensor] = []
@@ -417,6 +641,15 @@ class SegmentationModel(nn.Module):
         return self.m_network(image)
 
     def _step(self, stage: str, batch, threshold: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        if self.task == "multiclass":                # the threshold plays no part: the prediction is the argmax
+            pred = self._forward(batch["image"])
+            loss = self.f_criterion(pred, batch["mask"])
+            c = self._counts.get(stage)
+            if c is None:
+                c = self._counts[stage] = _StepConfusion(self.num_classes, getattr(self.f_criterion, "ignore_index", None), pred.device)
+            c.update(pred, batch["mask"])
+            self._loss.setdefault(stage, []).append(loss.detach())
+            return pred, loss
         if type(self.f_criterion) is BCEWithLogitsLoss and torch.is_grad_enabled():
             pred, loss = forward_loss(self.m_network, batch["image"], batch["mask"])      # loss inside the head's kernels
         else:
@@ -447,7 +680,14 @@ class SegmentationModel(nn.Module):
         the reference logs them: every step computes its own Accuracy / Dice / +IoU and ``self.log(..., on_epoch=True)``
         averages the per-step VALUES weighted by batch size (PLTrainer.py:88-96, 113-118) -- a mean of ratios, which is
         what ``ModelCheckpoint(monitor='val_dice')`` (PLTrainer.py:352) ranks checkpoints by.  The ratio of the epoch's
-        summed counts (what one would report for the whole split) is returned beside it under ``<stage>_*_pooled``."""
+        summed counts (what one would report for the whole split) is returned beside it under ``<stage>_*_pooled``.
+
+        ``task="multiclass"``: '<stage>_loss', '_acc', '_mean_iou', '_mean_dice' by the same rule -- every step's own
+        ``multiclass_metrics_from_confusion`` values (and its loss), averaged weighted by batch size -- beside
+        '<stage>_acc_pooled', '_mean_iou_pooled', '_mean_dice_pooled' and '_iou_per_class_pooled' from the summed matrix.  Raises
+        ``ValueError`` if a step met a target outside [0, num_classes) that was not the criterion's ``ignore_index``."""
+        if self.task == "multiclass":
+            return self._epoch_metrics_multiclass(stage, reset)
         out: Dict[str, float] = {}
         if stage in self._loss and self._loss[stage]:
             out[f"{stage}_loss"] = float(torch.stack(self._loss[stage]).mean())
@@ -464,6 +704,31 @@ class SegmentationModel(nn.Module):
             self._loss.pop(stage, None)
             if stage in self._counts:
                 self._counts[stage].reset()
+        return out
+
+    def _epoch_metrics_multiclass(self, stage: str, reset: bool) -> Dict[str, object]:
+        out: Dict[str, object] = {}
+        c = self._counts.get(stage)
+        if c is not None and c.n:
+            try:
+                rows, weights = c.rows()                     # the one host synchronisation
+                wsum = float(sum(weights))
+                K = self.num_classes
+                per = [multiclass_metrics_from_confusion(_split_counts(r, K)) for r in rows]
+                losses = self._loss.get(stage) or []
+                if len(losses) == len(weights):
+                    out[f"{stage}_loss"] = sum(w * v for w, v in zip(weights, torch.stack(losses).tolist())) / wsum
+                for k in ("acc", "mean_iou", "mean_dice"):
+                    out[f"{stage}_{k}"] = sum(w * m[k] for w, m in zip(weights, per)) / wsum
+                pooled = multiclass_metrics_from_confusion([[sum(r[i * K + j] for r in rows) for j in range(K)] for i in range(K)])
+                out.update({f"{stage}_acc_pooled": pooled["acc"], f"{stage}_mean_iou_pooled": pooled["mean_iou"],
+                            f"{stage}_mean_dice_pooled": pooled["mean_dice"], f"{stage}_iou_per_class_pooled": pooled["iou_per_class"]})
+            finally:
+                if reset:
+                    self._loss.pop(stage, None)
+                    c.reset()
+        elif reset:
+            self._loss.pop(stage, None)
         return out
 
 

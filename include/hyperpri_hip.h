@@ -581,6 +581,50 @@ int hpri_segmap_overlay(const float* image, long long sn, long long sc, long lon
                         int is_logits, float gamma, float inv_gamma, float alpha, float p0r, float p0g, float p0b, float p1r,
                         float p1g, float p1b, float p2r, float p2g, float p2b, unsigned char* rgb, unsigned char* classes,
                         hipStream_t stream);
+/* The multi-class picture: the same base picture (bands, clamp, NaN rule, gamma as above) under the colours of a uint8 class map
+ * (N, h, w), predicted (the `classes` output of hpri_seg_confusion) or true:
+ *     out_k = class == 0 ? base_k : alpha * palette[class][k] + (1 - alpha) * base_k;   rgb_k = (uint8)(out_k * 255 + 0.5f)
+ *   palette  K x 3 HOST floats in [0, 1] (row 0, the background's, is never shown); 2 <= K <= 64; a class value >= K paints as 0 */
+int hpri_segmap_classes(const float* image, long long sn, long long sc, long long sy, long long sx, int C, int band_r,
+                        int band_g, int band_b, const unsigned char* classes, int N, int h, int w, float gamma,
+                        float inv_gamma, float alpha, const float* palette, int K, unsigned char* rgb, hipStream_t stream);
+
+/* ---- the multi-class tail of a step (multiclass.hip; hyperpri_amd/trainer.py, evaluate.py) ----------------
+ * The counterpart of the BCE / seg_counts entries above for K class planes per pixel, 2 <= K <= 64 (anything else is an
+ * argument error, reported before any launch).
+ *   logits       contiguous NCHW fp32 (N, K, h, w), HW = h * w: class plane k of image n starts at (n*K + k)*HW
+ *   target       one class index per pixel, (N, HW); target_kind 0 = fp32 holding integers (truncated toward zero), 1 = uint8,
+ *                2 = int64
+ *   weight       K per-class weights on the device, or NULL (all 1)
+ *   use_ignore, ignore_index   pixels whose target equals ignore_index contribute nothing (use_ignore = 0: no such value)
+ * A target that is neither ignored nor inside [0, K) -- a NaN or out-of-range fp32 value included -- is INVALID.  It is checked
+ * before any use and never indexes the weight or the logits.  It cannot be reported without a host synchronisation, so it
+ * poisons the result: the cross-entropy becomes NaN (the gradient rows of such pixels are zero), the confusion pass counts it
+ * in counts[K*K].
+ *   hpri_softmax_ce_fwd   nn.CrossEntropyLoss(weight, ignore_index, reduction): per pixel lse = max + log(sum exp(x - max)) in
+ *                         one pass (running maximum and sum), l = w[t] * (lse - x_t).  Writes lse (N, HW) for the backward;
+ *                         loss[0] = mean ? sum l / sum w[t] : sum l (an all-ignored mean is 0 / 0 = NaN, as in torch);
+ *                         denom[0] = the divisor (1 for a sum), read by the backward; totals (nullable, 3 doubles on the
+ *                         device) accumulate sum l, sum w[t] and the invalid count across calls.  fp64 partial sums in a fixed
+ *                         order: bit-reproducible.  workspace: hpri_softmax_ce_workspace_doubles of N * HW doubles (pure host).
+ *   hpri_softmax_ce_bwd   with p_k = exp(x_k - lse), c = w[t] * grad_out / denom (grad_out: device scalar, NULL = 1):
+ *                         dlogits_k = p_k * c for k != t, dlogits_t = -(sum over j != t of p_j) * c -- never p_t - 1;
+ *                         exact zeros in all K planes of an ignored or invalid pixel.
+ *   hpri_seg_confusion    pred = argmax over the planes (lowest index among equal maxima, a NaN counts as the maximum: the
+ *                         rules of torch.argmax); counts[t*K + pred] += 1 (int64, K*K + 1 entries, accumulated across calls
+ *                         like hpri_seg_counts), counts[K*K] += invalid targets, ignored pixels skipped; classes (nullable):
+ *                         the uint8 class map (N, HW).  target and counts are both given or both NULL (a plain argmax).
+ * 16-byte accesses are used when HW % 4 == 0 and every base pointer is 16-byte aligned, element accesses otherwise; the
+ * results are the same bit for bit. */
+size_t hpri_softmax_ce_workspace_doubles(long long npix);
+int hpri_softmax_ce_fwd(const float* logits, const void* target, int target_kind, const float* weight, int N, int K,
+                        long long HW, int use_ignore, long long ignore_index, int mean, float* loss, float* lse, float* denom,
+                        double* totals, double* workspace, size_t ws_doubles, hipStream_t stream);
+int hpri_softmax_ce_bwd(const float* logits, const float* lse, const void* target, int target_kind, const float* weight, int N,
+                        int K, long long HW, int use_ignore, long long ignore_index, const float* denom, const float* grad_out,
+                        float* dlogits, hipStream_t stream);
+int hpri_seg_confusion(const float* logits, const void* target, int target_kind, int N, int K, long long HW, int use_ignore,
+                       long long ignore_index, long long* counts, unsigned char* classes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
