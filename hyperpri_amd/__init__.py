@@ -9,9 +9,9 @@ from .evaluate import (SplitPrediction, color_classmaps, color_segmaps, default_
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)
-from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, forward_loss, FusedAdam, FusedSGD, PRCurve, SegConfusion,  # noqa: F401
-                      SegCounts, SegmentationModel, argmax_classes, average_precision, load_checkpoint,
-                      multiclass_metrics_from_confusion, network_state_dict)
+from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss, FocalLoss, forward_loss, FusedAdam, FusedSGD,  # noqa: F401
+                      PRCurve, SegConfusion, SegCounts, SegLoss, SegmentationModel, TverskyLoss, argmax_classes, average_precision,
+                      load_checkpoint, multiclass_metrics_from_confusion, network_state_dict)
 
 __version__ = "0.1.0"
 

@@ -6,6 +6,7 @@ names and semantics follow ``RootLightningModel`` (PLTrainer.py:34-183) and its 
 library (``csrc/step.hip``) without a host synchronisation until a value is actually read.
 
     crit = BCEWithLogitsLoss()                       # drop-in for nn.BCEWithLogitsLoss() (params_HyperPRI.py:60)
+    crit = DiceBCELoss(pos_weight=3.0)               # or an imbalance-aware one (csrc/segloss.hip): SegLoss, DiceLoss, TverskyLoss, FocalLoss
     opt  = FusedAdam(net.parameters(), lr=1e-3)      # drop-in for optim.Adam (PLTrainer.py:171-174)
     model = SegmentationModel(net, crit, optimizer="Adam", lr=1e-3)
     loss = model.training_step({"image": x, "mask": m})
@@ -113,12 +114,189 @@ def forward_loss(network: nn.Module, image: torch.Tensor, target: torch.Tensor) 
     return pred, _BCEFn.apply(pred, target)
 
 
-class BCEWithLogitsLoss(nn.Module):
-    """``nn.BCEWithLogitsLoss()`` with mean reduction (params_HyperPRI.py:60,223): one fused pass forward
-    (fp64 partial sums in a fixed order -> bit-reproducible), one pass backward."""
+# ---------------------------------------------------------------------------------------------------
+# Imbalance-aware binary losses (csrc/segloss.hip): pos_weight, focal, Dice, Tversky and their weighted sums
+# ---------------------------------------------------------------------------------------------------
+def _scalar(v, what: str) -> float:
+    """A float, or a one-element tensor read once (at construction, never inside a step)."""
+    if isinstance(v, torch.Tensor):
+        if v.numel() != 1:
+            raise ValueError(f"{what} must be a float or a one-element tensor, got shape {tuple(v.shape)}")
+        return float(v.detach().reshape(()).cpu())
+    return float(v)
+
+
+class _SegLossFn(torch.autograd.Function):
+    """cfg = (w_point, pos_weight, focal_gamma, focal_alpha, mean, w_overlap, alpha, beta, s, tversky_gamma, per_image): the scalar
+    arguments of hpri_seg_loss_fwd in its order.  Returns (loss, terms); terms carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred: torch.Tensor, target: torch.Tensor, cfg: tuple):
+        _require_cuda(pred, "SegLoss input")
+        with torch.cuda.device(pred.device):
+            if target.dtype != torch.float32:
+                target = target.to(torch.float32)
+            x, y = _flat(pred, "SegLoss input"), _flat(target, "SegLoss target")
+            if x.shape != y.shape:
+                raise ValueError(f"Target size ({tuple(y.shape)}) must be the same as input size ({tuple(x.shape)})")
+            if x.dim() < 1 or x.numel() == 0:
+                raise ValueError(f"SegLoss: need (N, ...) logits with at least one element, got {tuple(x.shape)}")
+            n_img = int(x.shape[0])
+            hw = x.numel() // n_img
+            w_point, pos_weight, focal_gamma, focal_alpha, mean, w_overlap, alpha, beta, s, gamma_t, per_image = cfg
+            lib = _lib.load()
+            nws, nst = lib.hpri_seg_loss_workspace_doubles(n_img, hw), lib.hpri_seg_loss_state_doubles(n_img, int(per_image))
+            ws = torch.empty(nws, dtype=torch.float64, device=x.device)
+            state = torch.empty(nst, dtype=torch.float64, device=x.device)
+            loss = torch.empty((), dtype=torch.float32, device=x.device)
+            terms = torch.empty(3, dtype=torch.float32, device=x.device)
+            _lib.call("hpri_seg_loss_fwd", _p(x), _p(y), n_img, hw, w_point, pos_weight, focal_gamma, focal_alpha, int(mean), w_overlap,
+                      alpha, beta, s, gamma_t, int(per_image), _p(loss), _p(state), nst, _p(terms), _p(ws), nws, _stream())
+            ctx.save_for_backward(x, y, state)
+            ctx.cfg, ctx.shape = cfg, pred.shape
+            ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, gout: torch.Tensor, _gterms=None):
+        x, y, state = ctx.saved_tensors
+        w_point, pos_weight, focal_gamma, focal_alpha, _, w_overlap, _, _, _, _, per_image = ctx.cfg
+        with torch.cuda.device(x.device):
+            g = gout.contiguous().to(torch.float32)
+            dx = torch.empty_like(x)
+            n_img = int(x.shape[0])
+            _lib.call("hpri_seg_loss_bwd", _p(x), _p(y), n_img, x.numel() // n_img, w_point, pos_weight, focal_gamma, focal_alpha,
+                      w_overlap, int(per_image), _p(state), state.numel(), _p(g), _p(dx), _stream())
+        return dx.view(ctx.shape), None, None
+
+
+class SegLoss(nn.Module):
+    """The binary loss family of ``csrc/segloss.hip`` over fp32 logits ``x`` of any shape (N, ...) and a target ``y`` in [0, 1] of the
+    same shape (soft labels allowed; other dtypes are converted once)::
+
+        loss = bce_weight * R[ a_t * (1 - p_t)^focal_gamma * ce(x, y) ] + overlap_weight * mean_groups[ (1 - T_g)^tversky_gamma ]
+        ce   = pos_weight * y * softplus(-x) + (1 - y) * softplus(x)        a_t = focal_alpha*y + (1 - focal_alpha)(1 - y)  (None: 1)
+        T_g  = (I + smooth) / (I + tversky_alpha*(P - I) + tversky_beta*(Y - I) + smooth),   I = sum p*y, P = sum p, Y = sum y
+
+    ``R``: ``reduction`` "mean" or "sum" over all elements; a group is one image (``per_image=True``) or the whole batch.  ``smooth``
+    is the ``s`` of that formula: the usual Dice ``(2I + smooth) / (P + Y + smooth)`` is ``tversky_alpha = tversky_beta = 0.5`` with
+    half its ``smooth`` (what ``DiceLoss`` passes).  A weight of 0 drops its term: the kernels do not evaluate it.  One pass forward
+    (fp64 partial sums in a fixed order -> bit-reproducible), one pass backward, no host synchronisation; the module sits outside the
+    network's tape, so it works in every precision mode.  ``last_terms``: the last call's pointwise term, overlap term (both before
+    their weights) and mean ``T`` as a 3-element device tensor.  A group without any mass (``D == 0``) counts as ``T = 1``; ``T >= 1``
+    contributes 0 with a zero gradient."""
+
+    def __init__(self, bce_weight: float = 1.0, pos_weight=None, focal_gamma: float = 0.0, focal_alpha: Optional[float] = None,
+                 overlap_weight: float = 0.0, tversky_alpha: float = 0.5, tversky_beta: float = 0.5, smooth: float = 1.0,
+                 tversky_gamma: float = 1.0, per_image: bool = False, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"SegLoss: reduction must be 'mean' or 'sum', got {reduction!r}")
+        self.bce_weight, self.overlap_weight = float(bce_weight), float(overlap_weight)
+        self.pos_weight = 1.0 if pos_weight is None else _scalar(pos_weight, "pos_weight")
+        self.focal_gamma = float(focal_gamma)
+        self.focal_alpha = None if focal_alpha is None else float(focal_alpha)
+        self.tversky_alpha, self.tversky_beta = float(tversky_alpha), float(tversky_beta)
+        self.smooth, self.tversky_gamma = float(smooth), float(tversky_gamma)
+        self.per_image, self.reduction = bool(per_image), reduction
+        # (the launchers refuse the same values; here they are refused when the criterion is built)
+        if not self.pos_weight > 0:
+            raise ValueError(f"SegLoss: pos_weight must be positive, got {self.pos_weight}")
+        if not self.focal_gamma >= 0:
+            raise ValueError(f"SegLoss: focal_gamma must not be negative, got {self.focal_gamma}")
+        if self.focal_alpha is not None and not 0 <= self.focal_alpha <= 1:
+            raise ValueError(f"SegLoss: focal_alpha must lie in [0, 1] (None: no class balance), got {self.focal_alpha}")
+        if not (self.tversky_alpha >= 0 and self.tversky_beta >= 0 and self.tversky_alpha + self.tversky_beta > 0):
+            raise ValueError("SegLoss: tversky_alpha and tversky_beta must not be negative and not both 0")
+        if not self.smooth >= 0:
+            raise ValueError(f"SegLoss: smooth must not be negative, got {self.smooth}")
+        if not self.tversky_gamma > 0:
+            raise ValueError(f"SegLoss: tversky_gamma must be positive, got {self.tversky_gamma}")
+        if not (self.bce_weight == self.bce_weight and self.overlap_weight == self.overlap_weight) \
+                or (self.bce_weight == 0 and self.overlap_weight == 0):
+            raise ValueError("SegLoss: bce_weight and overlap_weight are both 0: nothing to compute")
+        self.last_terms: Optional[torch.Tensor] = None
+
+    def config(self) -> tuple:
+        """The scalar arguments of ``hpri_seg_loss_fwd``, in its order."""
+        return (self.bce_weight, self.pos_weight, self.focal_gamma, -1.0 if self.focal_alpha is None else self.focal_alpha,
+                self.reduction == "mean", self.overlap_weight, self.tversky_alpha, self.tversky_beta, self.smooth, self.tversky_gamma,
+                self.per_image)
 
     def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:   # noqa: A002 (torch's names)
+        loss, self.last_terms = _SegLossFn.apply(input, target, self.config())
+        return loss
+
+    def extra_repr(self) -> str:
+        return ", ".join(f"{k}={getattr(self, k)}" for k in ("bce_weight", "pos_weight", "focal_gamma", "focal_alpha", "overlap_weight",
+                                                             "tversky_alpha", "tversky_beta", "smooth", "tversky_gamma", "per_image",
+                                                             "reduction"))
+
+
+class DiceLoss(SegLoss):
+    """Soft Dice, ``1 - (2 I + smooth) / (P + Y + smooth)`` over the batch (or the mean over the images: ``per_image``)."""
+
+    def __init__(self, smooth: float = 1.0, per_image: bool = False):
+        super().__init__(bce_weight=0.0, overlap_weight=1.0, tversky_alpha=0.5, tversky_beta=0.5, smooth=float(smooth) / 2, per_image=per_image)
+
+
+class TverskyLoss(SegLoss):
+    """``(1 - T)^gamma`` with ``T = (I + smooth) / (I + alpha * FP + beta * FN + smooth)``, FP = P - I, FN = Y - I; ``gamma != 1``: the
+    focal Tversky loss."""
+
+    def __init__(self, alpha: float = 0.5, beta: float = 0.5, smooth: float = 1.0, gamma: float = 1.0, per_image: bool = False):
+        super().__init__(bce_weight=0.0, overlap_weight=1.0, tversky_alpha=alpha, tversky_beta=beta, smooth=smooth, tversky_gamma=gamma,
+                         per_image=per_image)
+
+
+class FocalLoss(SegLoss):
+    """torchvision's ``sigmoid_focal_loss(input, target, alpha, gamma, reduction)``; a negative ``alpha`` (or None) switches the class
+    balance off, as there."""
+
+    def __init__(self, gamma: float = 2.0, alpha: Optional[float] = 0.25, reduction: str = "mean"):
+        super().__init__(focal_gamma=gamma, focal_alpha=None if alpha is None or alpha < 0 else alpha, reduction=reduction)
+
+
+class DiceBCELoss(SegLoss):
+    """``bce_weight * BCEWithLogits(pos_weight) + dice_weight * Dice(smooth)`` in the same two passes."""
+
+    def __init__(self, bce_weight: float = 1.0, dice_weight: float = 1.0, pos_weight=None, smooth: float = 1.0, per_image: bool = False):
+        super().__init__(bce_weight=bce_weight, pos_weight=pos_weight, overlap_weight=dice_weight, smooth=float(smooth) / 2,
+                         per_image=per_image)
+
+
+class BCEWithLogitsLoss(nn.Module):
+    """``nn.BCEWithLogitsLoss(pos_weight=None, reduction="mean")`` (params_HyperPRI.py:60,223): one fused pass forward
+    (fp64 partial sums in a fixed order -> bit-reproducible), one pass backward.  ``pos_weight``: a float or a one-element tensor;
+    ``reduction``: "mean" or "sum".  With the defaults this is the unweighted mean of ``csrc/step.hip`` -- the one form the network's
+    head can compute itself (``forward_loss``; ``fusable``); any other argument runs ``SegLoss``.  "Default" means the arguments
+    left at their defaults: ``pos_weight=1.0`` (or a tensor holding 1) is the same loss mathematically but is taken as a weighted
+    one -- it runs ``SegLoss`` (another summation order, so other last bits) and ``SegmentationModel`` does not hand it to the fused
+    head.  Pass ``pos_weight=None`` to keep the fused head."""
+
+    def __init__(self, pos_weight=None, reduction: str = "mean"):
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"BCEWithLogitsLoss: reduction must be 'mean' or 'sum', got {reduction!r}")
+        self.pos_weight = None if pos_weight is None else _scalar(pos_weight, "pos_weight")
+        self.reduction = reduction
+        self._seg = None if pos_weight is None and reduction == "mean" else SegLoss(pos_weight=self.pos_weight, reduction=reduction)
+
+    @property
+    def fusable(self) -> bool:
+        """True for the default configuration only: the loss ``forward_loss`` computes inside the head's kernels."""
+        return self._seg is None
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:   # noqa: A002 (torch's names)
+        if self._seg is not None:
+            return self._seg(input, target)
         return _BCEFn.apply(input, target)
+
+
+def _takes_fused_head(criterion: nn.Module) -> bool:
+    """Only a default-configured ``BCEWithLogitsLoss`` (no subclass) is what ``forward_loss`` computes: a weighted or sum-reduced one
+    must never be replaced by the unweighted fused loss."""
+    return type(criterion) is BCEWithLogitsLoss and criterion.fusable
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -650,7 +828,7 @@ class SegmentationModel(nn.Module):
             c.update(pred, batch["mask"])
             self._loss.setdefault(stage, []).append(loss.detach())
             return pred, loss
-        if type(self.f_criterion) is BCEWithLogitsLoss and torch.is_grad_enabled():
+        if _takes_fused_head(self.f_criterion) and torch.is_grad_enabled():
             pred, loss = forward_loss(self.m_network, batch["image"], batch["mask"])      # loss inside the head's kernels
         else:
             pred = self._forward(batch["image"])

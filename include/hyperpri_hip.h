@@ -626,6 +626,41 @@ int hpri_softmax_ce_bwd(const float* logits, const float* lse, const void* targe
 int hpri_seg_confusion(const float* logits, const void* target, int target_kind, int N, int K, long long HW, int use_ignore,
                        long long ignore_index, long long* counts, unsigned char* classes, hipStream_t stream);
 
+/* ---- imbalance-aware binary losses (segloss.hip; hyperpri_amd/trainer.py: SegLoss and its subclasses) --------
+ * One family over contiguous fp32 logits x and fp32 targets y in [0, 1] (soft labels allowed), n_img images of hw elements:
+ *     loss = w_point * R_elems[ a_t * (1 - p_t)^focal_gamma * ce(x, y) ] + w_overlap * mean_groups[ (1 - T_g)^tversky_gamma ]
+ *     ce(x, y) = pos_weight * y * softplus(-x) + (1 - y) * softplus(x);   1 - p_t = y * sigmoid(-x) + (1 - y) * sigmoid(x)
+ *     a_t = focal_alpha * y + (1 - focal_alpha) * (1 - y)                  (focal_alpha < 0: a_t = 1)
+ *     T_g = (I + s) / D,  D = I + alpha * (P - I) + beta * (Y - I) + s,  I = sum p*y, P = sum p, Y = sum y over group g, p = sigmoid(x)
+ * R_elems: the mean (mean != 0) or the sum over all elements; a group: one image (per_image != 0) or the whole batch; s = smooth.
+ * Dice is alpha = beta = 1/2 (the usual (2I + smooth) / (P + Y + smooth) has s = smooth / 2); focal_gamma = 0 with pos_weight != 1
+ * is weighted BCE.  A weight of 0 drops its term: the kernels do not evaluate it.  Edge rules: D == 0 gives T = 1; T >= 1 gives a
+ * term of 0 with derivative 0.
+ *   hpri_seg_loss_fwd   one pass over x and y (fp64 partial sums per workgroup in a fixed order, no floating-point atomics:
+ *                       bit-reproducible) and a one-workgroup finalize.  loss[0]: the loss; terms[0..2]: R_elems[...] and
+ *                       mean_groups[...] before their weights (0 for a dropped term) and the mean of T_g;  state: what the backward
+ *                       reads, hpri_seg_loss_state_doubles doubles -- state[0] = w_point (/ (n_img * hw) for a mean), then per
+ *                       group c1_g, c0_g with  c1_g = w_overlap / G * dL/dT_g * (D - (I + s)(1 - alpha - beta)) / D^2,
+ *                       c0_g = w_overlap / G * dL/dT_g * (-(I + s) * alpha) / D^2,  dL/dT = -gamma_t * (1 - T)^(gamma_t - 1).
+ *                       workspace: hpri_seg_loss_workspace_doubles(n_img, hw) doubles (pure host functions, both).
+ *   hpri_seg_loss_bwd   dlogits_i = grad_out * [ state[0] * d(pointwise_i)/dx_i + (c1_g * y_i + c0_g) * sigmoid(x_i) * sigmoid(-x_i) ]
+ *                       in one pass, the focal derivative analytic for any y; grad_out: device scalar, NULL = 1.  The pointwise
+ *                       parameters, the two weights and per_image must be those of the forward.
+ * No host synchronisation anywhere.  16-byte accesses when hw % 4 == 0 and every base pointer is 16-byte aligned, element accesses
+ * otherwise, bit-identical results.  Argument errors, reported before any launch: a null pointer, a size <= 0, pos_weight <= 0,
+ * focal_gamma < 0, focal_alpha > 1, alpha < 0, beta < 0, alpha + beta == 0, smooth < 0, tversky_gamma <= 0, both weights 0, a
+ * workspace that is too small, a state buffer (state_doubles: its size in doubles, forward and backward) smaller than
+ * hpri_seg_loss_state_doubles(n_img, per_image). */
+size_t hpri_seg_loss_workspace_doubles(int n_img, long long hw);
+size_t hpri_seg_loss_state_doubles(int n_img, int per_image);
+int hpri_seg_loss_fwd(const float* logits, const float* target, int n_img, long long hw, float w_point, float pos_weight,
+                      float focal_gamma, float focal_alpha, int mean, float w_overlap, float tversky_alpha, float tversky_beta,
+                      float smooth, float tversky_gamma, int per_image, float* loss, double* state, size_t state_doubles,
+                      float* terms, double* workspace, size_t ws_doubles, hipStream_t stream);
+int hpri_seg_loss_bwd(const float* logits, const float* target, int n_img, long long hw, float w_point, float pos_weight,
+                      float focal_gamma, float focal_alpha, float w_overlap, int per_image, const double* state,
+                      size_t state_doubles, const float* grad_out, float* dlogits, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
