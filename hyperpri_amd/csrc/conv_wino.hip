@@ -465,6 +465,13 @@ extern "C" int hpri_conv_wino(const float* x, int x_cs, int x_coff, const float*
 //   stage      one strip of 16 tiles (2 output rows x 32 columns): input halo 4 x 34 pixels x 64 cin and dY 2 x 32 pixels
 //              x 64 cout, both [pixel][channel] by LDS-DMA (lanes index the channel: every ds_read_b32 is 32 consecutive
 //              dwords), double buffered; 64 MFMAs per wave, one barrier.
+//   edge       the last strip of a strip row hangs over the right image edge; its dY beyond W is zero-filled, so dM = A 0 A^T = 0
+//              there.  MFMA k-step kk multiplies the pixel columns x0 + 4 kk .. + 3: a strip runs kend = min(8, ceil((W - x0) / 4))
+//              k-steps (wave-uniform; a k-step is left out only when ALL four of its columns are >= W).  Accumulators start at
+//              +0 and a left-out k-step would have added va * (+-0) = +-0, which leaves every bit of a round-to-nearest sum as
+//              it is: slabs and gradients are bit-identical to running all 8 -- for FINITE activations.  A non-finite x in the
+//              halo column right of the edge-most valid one (Inf * 0) gave NaN when all 8 ran and does not now.
+//              Option wgrad_skip_edge = 0 (api.cpp) sets the bound to the strips' own width: 8 k-steps everywhere.
 struct WinoWgradArgs {
   const float* x; int x_cs, x_coff, x_cvalid;
   const float* dy; int dy_cs, dy_coff, dy_cvalid;
@@ -472,6 +479,7 @@ struct WinoWgradArgs {
   int N, H, W, Cr, Nr, cblk;
   int strips_x, strips_y, total, per_split;
   int ntile, items, per_xcd;    // (c, n) tiles per split; work items; items per XCD band
+  int kw;                       // image columns that bound a strip's k-steps: W (option wgrad_skip_edge) or strips_x * 32 (all 8)
 };
 
 #define WG_XROW 36               // staged halo pixels per row (34 used)
@@ -528,6 +536,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
     const int sx_ = q_ % a.strips_x; q_ /= a.strips_x;                                                                 \
     const int sy_ = q_ % a.strips_y; const int img_ = q_ / a.strips_y;                                                 \
     const int y0_ = sy_ * 2, x0_ = sx_ * 32;                                                                           \
+    kend_next = min(8, (a.kw - x0_ + 3) >> 2);                /* k-steps of this unit (wave-uniform) */                \
     unsigned char* lb_ = smem + (buf_) * WG_STAGE_BYTES;                                                               \
     const float* xu_ = a.x + ((long long)(img_ * a.H + y0_ - 1) * a.W + x0_ - 1) * a.x_cs + a.x_coff + c_blk;          \
     const float* yu_ = a.dy + ((long long)(img_ * a.H + y0_) * a.W + x0_) * a.dy_cs + a.dy_coff + n_blk;               \
@@ -553,8 +562,14 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 // 0 or +-1 -- a = 0: dY[0], a = 1: dY[0] + dY[1], a = 2: dY[0] - dY[1], a = 3: -dY[1] -- so rows 0 and 3 need no arithmetic at
 // all and rows 1, 2 one add per column; the column part for b = 2 fb + e is t0 | t0 + t1 (fb = 0), t0 - t1 | -t1 (fb = 1).  The
 // two minus signs (row 3, and b = 3) are left out here and applied once to the accumulators when the slab is written.
-#define K_LOOP(FA_, FB_)                                                                                               \
-    _Pragma("unroll 2") for (int kk = 0; kk < 8; ++kk) {      /* MFMA k-step: tiles 2 kk + lh of the strip */            \
+// ONE loop with the unit's trip count kend (odd at W = 121 and W = 60: exact, no remainder step).  hipcc does not unroll it
+// (`unroll 2` with the constant trip count 8 gave 16 MFMAs, 40-61 vector and 16-20 LDS instructions per two k-steps; this gives 8,
+// 19-29 and 8-10 per k-step, 185 registers either way).  A second copy of the loop for short strips (constant-trip loop for
+// kend = 8, runtime loop otherwise) inside the unit loop spills 2044 registers, with or without an opaque lane id: rejected.
+// Two k-steps per trip plus a straight-line odd step keeps the unrolled schedule (the second k-step's reads among the first one's
+// MFMAs) at 4-5 more vector instructions per pair, and measured no faster than running all 8 (experiments/README.md).
+#define K_STEP(FA_, FB_)                                      /* MFMA k-step kk: tiles 2 kk + lh of the strip */         \
+    {                                                                                                                  \
       const int tile = 2 * kk + lh;                                                                                    \
       float va[2][2], vb[2][2];                     /* [frequency e][cin tile | cout tile] */                          \
       _Pragma("unroll") for (int ct = 0; ct < 2; ++ct) {                                                               \
@@ -591,11 +606,13 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
   for (int u = u0; u < u1; ++u) {                                                                                      \
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                   \
     __builtin_amdgcn_s_barrier();          /* this unit has landed for everyone; the other buffer is free */           \
+    const int kend = kend_next;                                                                                        \
     if (u + 1 < u1) LOAD_UNIT(u + 1, (u + 1 - u0) & 1)                                                                 \
     const float* xs = reinterpret_cast<const float*>(smem + ((u - u0) & 1) * WG_STAGE_BYTES);                          \
     const float* ys = xs + WG_X_BYTES / 4;                                                                             \
-    K_LOOP(FA_, FB_)                                                                                                   \
+    _Pragma("unroll 2") for (int kk = 0; kk < kend; ++kk) K_STEP(FA_, FB_)                                             \
   }
+  int kend_next = 8;
   if (u0 < u1) LOAD_UNIT(u0, 0)
   switch (wave) {                          // wave = 2 fa + fb
     case 0: UNIT_LOOP(0, 0) break;
@@ -608,7 +625,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
     default: UNIT_LOOP(3, 1) break;
   }
 #undef UNIT_LOOP
-#undef K_LOOP
+#undef K_STEP
 #undef LOAD_UNIT
   // slab: ws[split][xi][c][n]; accumulator rows = cin (register index), columns = cout (lane)
   float* slab = a.ws + (size_t)split * 16 * a.Cr * a.Nr;
@@ -771,6 +788,7 @@ extern "C" int hpri_conv_wino_wgrad(const float* x, int x_cs, int x_coff, int x_
   a.per_split = hpri_cdiv(a.total, splits);
   a.ntile = a.cblk * (a.Nr / 64);
   a.items = splits * a.ntile; a.per_xcd = hpri_cdiv(a.items, 8);
+  a.kw = hpri_option(6) != 0 ? W : a.strips_x * 32;           // wgrad_skip_edge: no MFMAs for pixel columns right of the image
   dim3 grid((unsigned)(a.per_xcd * 8), 1u, 1u);
   hipLaunchKernelGGL(conv_wino_wgrad_kernel, grid, dim3(512), 0, stream, a);
   HPRI_CHECK_LAUNCH();

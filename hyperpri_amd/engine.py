@@ -1865,7 +1865,11 @@ def _wgrad(x: Act, dy: Act, dw: torch.Tensor, accumulate: int, cin: int, cout: i
         wtag = "conv_wgrad_winograd_f32<3>"
         if SHAPE_TAGS:
             wtag += f" N{N} {H}x{W} C{cin_pad} N{cout}"
-        with _timed(wtag, 2.0 * N * H * W * cin * cout * 9, executed=2.0 * N * ((H + 1) // 2) * ((W + 1) // 2) * 16 * cin * cout):
+        # executed: the MFMA k-steps the kernel runs, two tiles each -- 8 per 32-column strip, and in the last strip of a strip
+        # row only those that hold a column of the image (option wgrad_skip_edge; all 8 with the option off)
+        sx = (W + 31) // 32
+        ksteps = 8 * sx if _lib.current().hpri_get_option(b"wgrad_skip_edge") == 0 else 8 * (sx - 1) + (W - 32 * (sx - 1) + 3) // 4
+        with _timed(wtag, 2.0 * N * H * W * cin * cout * 9, executed=2.0 * N * ((H + 1) // 2) * (2 * ksteps) * 16 * cin * cout):
             _lib.call("hpri_conv_wino_wgrad", x.ptr, x.cs, x.coff, cin_pad, dy.ptr, dy.cs, dy.coff, dy.cw, _p(wws), wws.numel(),
                       N, H, W, cin_pad, cout_pad, _stream())
         _lib.call("hpri_wino_wgrad_reduce", _p(wws), _p(dw), N, H, W, cin, cin_pad, cout, cout_pad, accumulate, _stream())

@@ -46,7 +46,10 @@ int hpri_version(void);
  * from which the conv / weight-gradient kernels switch to their XCD-aware 1-D grids -- and "wgrad_cu_reserve": compute
  * units the fp32 Winograd weight gradient (one workgroup per CU, grids planned as exact multiples of the CU count) leaves to other
  * kernels, e.g. the channels of a collective that runs beside the backward (0 = none).  Results do not depend
- * on them, only block order and (for weight gradients) the number of partial slabs, i.e. the summation order. */
+ * on them, only block order and (for weight gradients) the number of partial slabs, i.e. the summation order.
+ * "wgrad_skip_edge" (default 1): the fp32 Winograd weight gradient leaves out the MFMA k-steps whose four pixel columns all lie
+ * right of the image edge, where dY is zero-filled; 0 runs every k-step of every strip.  Bit-identical results for finite
+ * activations (a non-finite activation in the column beyond the edge-most valid one gives NaN only with 0). */
 int hpri_set_option(const char* name, int value);
 /* A non-blocking stream of the lowest priority the current device offers (*priority receives it); the caller owns it. */
 
