@@ -12,17 +12,13 @@ import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-DIAG = os.environ.get("HPRI_DIAG", "0") == "1"      # the diagnostics build (hyperpri_amd/build.py, include/hyperpri_hip_diag.h)
-LIB_PATH = os.path.join(_HERE, "lib", "libhyperpri_hip_diag.so" if DIAG else "libhyperpri_hip.so")
+LIB_PATH = os.path.join(_HERE, "lib", "libhyperpri_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hyperpri_hip.h")
-DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "hyperpri_hip_diag.h")
-
 LIB_F16_PATH = os.path.join(_HERE, "lib", "libhyperpri_hip_f16.so")      # the same sources with IEEE half as the 16-bit type (precision "f16")
 
 _lock = threading.Lock()
 _lib = None
 _lib_f16 = None
-_decls = None
 _tls = threading.local()        # .kind: which library the calls of this thread go to ("f16" inside an f16-mode tape, see ``using``)
 
 
@@ -61,9 +57,19 @@ def parse_header(path: str = HEADER_PATH):
     return out
 
 
+def _bind(path: str):
+    """dlopen ``path`` and give every function the header declares its C types."""
+    lib = ctypes.CDLL(path)
+    for name, (restype, argtypes) in parse_header().items():
+        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+        fn.restype = restype
+        fn.argtypes = argtypes
+    return lib
+
+
 def load():
     """Load (once) and return the ctypes library; raises if it has not been built."""
-    global _lib, _decls
+    global _lib
     if _lib is not None:
         return _lib
     with _lock:
@@ -74,15 +80,7 @@ def load():
                 f"hyperpri_amd: HIP extension not built ({LIB_PATH} missing). Run "
                 "`python -m hyperpri_amd.build` (needs hipcc, --offload-arch=gfx950). "
                 "There is no CPU/PyTorch fallback for the hot path.")
-        lib = ctypes.CDLL(LIB_PATH)
-        _decls = parse_header()
-        if DIAG:
-            _decls.update(parse_header(DIAG_HEADER_PATH))
-        for name, (restype, argtypes) in _decls.items():
-            fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _lib = lib
+        _lib = _bind(LIB_PATH)
     return _lib
 
 
@@ -97,12 +95,7 @@ def load_f16():
             return _lib_f16
         if not os.path.exists(LIB_F16_PATH):
             raise RuntimeError(f"hyperpri_amd: precision 'f16' needs {LIB_F16_PATH} (python -m hyperpri_amd.build)")
-        lib = ctypes.CDLL(LIB_F16_PATH)
-        for name, (restype, argtypes) in parse_header().items():
-            fn = getattr(lib, name)
-            fn.restype = restype
-            fn.argtypes = argtypes
-        _lib_f16 = lib
+        _lib_f16 = _bind(LIB_F16_PATH)
     return _lib_f16
 
 

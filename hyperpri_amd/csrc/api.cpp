@@ -81,28 +81,6 @@ int hpri_cu_count() {
   return n;
 }
 
-#ifdef HPRI_DIAG_KERNELS   // measured neutral (round 3): diagnostics build only
-// A stream of the LOWEST priority the device offers, for work that should only fill what the caller's stream leaves free
-// (the engine's weight-gradient stream: its 256-workgroup launches otherwise hold every CU while the 2-64-workgroup finalize
-// kernels on the critical path wait for a slot).  *stream receives a hipStream_t the caller owns (hpri_stream_destroy).
-extern "C" int hpri_stream_create_low_priority(void** stream, int* priority) {
-  HPRI_REQUIRE(stream != nullptr, "stream_create_low_priority: null pointer");
-  int least = 0, greatest = 0;
-  if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return hpri_set_error(HPRI_ERR_LAUNCH, "stream priority range query failed");
-  hipStream_t s = nullptr;
-  if (hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) != hipSuccess) return hpri_set_error(HPRI_ERR_LAUNCH, "stream creation failed");
-  *stream = reinterpret_cast<void*>(s);
-  if (priority != nullptr) *priority = least;
-  return HPRI_OK;
-}
-extern "C" int hpri_stream_destroy(void* stream) {
-  if (stream != nullptr && hipStreamDestroy(reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
-    return hpri_set_error(HPRI_ERR_LAUNCH, "stream destruction failed");
-  return HPRI_OK;
-}
-
-#endif   // HPRI_DIAG_KERNELS
-
 // ---- item queues of the persistent kernels (common.h) ------------------------------------------------------------------------------
 // stream -> caller-owned counter buffer + the parity of the next launch.  A small table under a mutex: launchers take their half
 // right before the launch (a handful of entries; the engine registers one buffer per stream it launches on).

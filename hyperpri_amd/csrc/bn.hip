@@ -765,24 +765,6 @@ extern "C" int hpri_bn_relu_bwd_fused(const float* partials, int part_blocks, in
                           pix_per_group, C, Cw, relu, use_batch_stats, planes, plane_stride, pl_cs, pl_coff, pl_cw, npl, stream);
 }
 
-#ifdef HPRI_DIAG_KERNELS   // counterpart of hpri_conv_bf16v3_bnred (diagnostics build only)
-// hpri_bn_relu_bwd_fused with the pre-BN tensor stored as bf16 (partial sums from hpri_conv_bf16v3_bnred)
-extern "C" int hpri_bn_relu_bwd_fused_x16(const float* partials, int part_blocks, int part_cpart, const float* dy, int dy_cs, int dy_coff,
-                                          const void* x16, int x_cs, int x_coff, float* dx, int dx_cs, int dx_coff, const float* mean,
-                                          const float* invstd, const float* scale, const float* shift, float* dgamma, float* dbeta,
-                                          int accumulate_param_grads, float* dbias, int accumulate_dbias, float* workspace,
-                                          size_t ws_floats, long long P, long long pix_per_group, int C, int Cw, int relu,
-                                          int use_batch_stats, void* planes, long long plane_stride, int pl_cs, int pl_coff,
-                                          int pl_cw, int npl, hipStream_t stream) {
-  HPRI_REQUIRE(partials != nullptr, "bn_relu_bwd_fused_x16: null partial sums");
-  HPRI_REQUIRE(((uintptr_t)x16 & 7) == 0, "bn_relu_bwd_fused_x16: the bf16 tensor must be 8-byte aligned");
-  return bn_relu_bwd_impl(partials, part_blocks, part_cpart, dy, dy_cs, dy_coff, reinterpret_cast<const float*>(x16), true, x_cs, x_coff, false, dx,
-                          dx_cs, dx_coff, mean, invstd, scale, shift, dgamma, dbeta, accumulate_param_grads, dbias, accumulate_dbias,
-                          workspace, ws_floats, P, pix_per_group, C, Cw, relu, use_batch_stats, planes, plane_stride, pl_cs, pl_coff,
-                          pl_cw, npl, stream);
-}
-#endif   // HPRI_DIAG_KERNELS
-
 // the same with the pre-BN tensor stored as bf16 (see hpri_bn_apply_relu_x16)
 extern "C" int hpri_bn_relu_bwd_x16(const float* dy, int dy_cs, int dy_coff, const void* x16, int x_cs, int x_coff,
                                     float* dx, int dx_cs, int dx_coff, const float* mean, const float* invstd,

@@ -65,7 +65,7 @@ enum { HPRI_E_DIRECT = 0, HPRI_E_D2S = 1 };   // D2S: scatter 2x2 stride-2 patch
 
 // Optional second output of the element-wise producers: the same values as bf16 NHWC planes (hi | hi,lo | hi,mid,lo:
 // plane k = bf16 of what the previous planes left), which the bf16-mode convolutions stage by LDS-DMA
-// (conv_bf16v2.hip).  Channels [C, cw) of the planes are zero-filled by the producer.
+// (conv_bf16v3.hip).  Channels [C, cw) of the planes are zero-filled by the producer.
 typedef h16_t bf16x4_t __attribute__((ext_vector_type(4)));
 struct PlaneOut { h16_t* p; long long plane; int cs, coff, cw, npl; };
 

@@ -1,9 +1,9 @@
 // 3x3 implicit-GEMM convolution on bf16 activation PLANES, third form (precision mode "bf16"; forward, and data gradient with the
-// mode-1 pack; reference model_parts.py:22,25; models.py:169,177 and their autograd) -- conv_bf16v2.hip rebuilt on the occupancy
+// mode-1 pack; reference model_parts.py:22,25; models.py:169,177 and their autograd), built on the occupancy
 // recipe that worked for the fp32 Winograd kernel (conv_wino4.hip):
 //
 //   workgroup  256 threads = 4 waves, 256 pixels x 64 output channels, 72 KB of LDS: TWO independent workgroups per CU (one wave
-//              of each on every SIMD).  v2 ran one 8-wave workgroup per CU: every barrier and the whole store + statistics
+//              of each on every SIMD).  Its predecessor ran one 8-wave workgroup per CU: every barrier and the whole store + statistics
 //              epilogue (~10 k cycles per item) stalled the CU's matrix pipes; here they run under the partner workgroup's
 //              MFMAs.  Persistent (2 x CUs workgroups walking fixed item lists): a first, non-persistent form paid ~9 k cycles
 //              of dispatch gap and ~5 k of exposed prologue per item (tools/v3_stamps.py); now the next item's first halo and
@@ -17,13 +17,13 @@
 //   A (input)  halo of (TH+2) x (TW+2) pixels x 32 channels, 64-byte pixel rows, by LDS-DMA (buffer_load ... lds, out-of-image
 //              pixels zero-filled by the descriptor's range check); the four 16-byte k-slots of a pixel are XOR-swizzled with
 //              2*((pixel>>2)&1) through the DMA source address: conflict-free ds_read_b128 for the 16x16x32 fragment lane
-//              groups at every tap offset (brute-forced over all halo positions; v2's (pixel>>2)&3 is 2-way conflicted for
+//              groups at every tap offset (brute-forced over all halo positions; (pixel>>2)&3 is 2-way conflicted for
 //              this lane map).  Double-buffered per 32-channel chunk, the next chunk's halo issued in two halves.
 //   B (weights) one kernel row (3 taps x 64 ch x 32 k = 12 KB) per stage, same swizzle, double-buffered, one stage ahead.
 //   pipeline   one counted vmcnt + ONE barrier per stage of 48 MFMAs per wave; DMA pieces issued between the MFMAs.
 //   statistics per-tile BatchNorm partials (exact two-pass per wave, Chan merge of the four waves) with DPP row reductions:
 //              the 16 pixels of an accumulator column live on the 16 lanes of a DPP row.
-// Epilogue contract (bias, ReLU, accumulate, split-K raw slabs, statistics records) as conv_bf16v2.hip.
+// Epilogue contract (bias, ReLU, accumulate, split-K raw slabs, statistics records): hpri_conv_bf16v3 at the end of this file.
 #include "common.h"
 
 typedef h16_t bf16x8 __attribute__((ext_vector_type(8)));
@@ -47,17 +47,10 @@ struct ConvV3Args {
   int seg_twl[V3_MAXSEG], seg_xbeg[V3_MAXSEG], seg_ntx[V3_MAXSEG], seg_first[V3_MAXSEG];
   int ncu, stagger_cycles;                   // compute units of the device; one-off delay of each CU's second occupant
   unsigned *queue, *queue_clear;             // item counters of this launch and the half it zeroes for the next one (common.h), or nullptr = fixed item lists
-  // conv_bf16v3_kernel<true> (a data-gradient launch that writes the ONLY contribution to dL/dx, x = ReLU(BN(bn_x))): the epilogue
-  // also reads the pre-BN tensor bn_x (bf16, elements per pixel bn_x_cs, first channel bn_x_coff, bn_cw readable channels) at its
-  // output positions and leaves per-tile partial sums of that BatchNorm's backward, bn_part[stat tile][2][bn_cpart] =
-  // (sum g*[y>0], sum g*[y>0]*xhat): the stage that produced x then skips its two reduction sweeps (hpri_bn_relu_bwd_fused)
   // second output: channels [y2_c0, y2_c0 + y2_cw) (whole 64-channel blocks) of the result ALSO (y2_only: ONLY) as bf16 rows of
   // y2_cs elements from y2_coff on -- the gradient of the upsampled half of a decoder concat, which its readers (the transposed
   // convolution's data and weight gradient: gemm_bf16v3.hip, wgrad_bf16v3.hip) stage as planes
   h16_t* y2; int y2_cs, y2_coff, y2_c0, y2_cw, y2_only;
-  const h16_t* bn_x; int bn_x_cs, bn_x_coff, bn_cw, bn_relu, bn_cpart;
-  const float *bn_mean, *bn_invstd, *bn_scale, *bn_shift;
-  float* bn_part;
 #ifdef HPRI_STAMPS
   unsigned long long* stamps;                // diagnostic builds only: [workgroup][16] stamps of wave 0 (tools/v3_stamps.py)
 #endif
@@ -92,7 +85,6 @@ __device__ __forceinline__ float v3_row_sum(float v) {
 // Geometry of one work item (256-pixel tile x 64-channel block); wave-uniform.
 struct V3Tile { int img, y0, x0, xlim, twl, nb, bx; };
 
-template <bool BNRED>
 __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * V3_A_BYTES + 2 * V3_B_BYTES + 512 + 16 + 16];
   unsigned char* a_lds = smem;
@@ -438,25 +430,6 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
     // inside the written width" (everywhere except the last block of a narrow tensor): the common path has no per-store
     // condition at all.
     const bool full = cur.nb * 64 + 64 <= dcw;
-    // BatchNorm-backward partial sums (see ConvV3Args): the pre-BN values at this lane's 4 pixels x 16 channels and the block's 64
-    // parameter quadruples are requested BEFORE the stores (vmcnt counts in order: a load behind a store waits for the store)
-    bf16x4_t xq[4][4];
-    f32x4 prm4 = {0.f, 0.f, 0.f, 0.f};
-    if (BNRED) {
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt) {
-        const int p = (wave * 4 + mt) * 16 + li;
-        const int iy = min(cur.y0 + (p >> twl), a.H - 1), ix = min(cur.x0 + (p & (TW - 1)), a.W - 1);
-        const h16_t* xr = a.bn_x + ((size_t)(cur.img * a.H + iy) * a.W + ix) * a.bn_x_cs + a.bn_x_coff;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt)      // channels beyond the readable width: any in-bounds quad (their g is an exact zero)
-          xq[mt][nt] = *reinterpret_cast<const bf16x4_t*>(xr + min(nlane + nt * 16, a.bn_cw - 4));
-      }
-      if (tid < 64) {
-        const int n = min(cur.nb * 64 + tid, a.Cout - 1);
-        prm4 = f32x4{a.bn_scale[n], a.bn_shift[n], a.bn_mean[n], a.bn_invstd[n]};
-      }
-    }
 #define V3_STORE_LOOP(ACC_, COND_)                                                                                    \
   if (ACC_) {               /* all loads first: a wait for a load behind a store would wait for the store as well */  \
     f32x4 old_[4][4];                                                                                                 \
@@ -473,7 +446,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
           if (COND_) *reinterpret_cast<f32x4*>(prow[mt] + nt * 16) = acc[mt][nt];                                     \
     }                                                                                                                 \
   }
-    const bool to_y2 = !BNRED && !raw && a.y2 != nullptr && cur.nb * 64 >= a.y2_c0 && cur.nb * 64 < a.y2_c0 + a.y2_cw;
+    const bool to_y2 = !raw && a.y2 != nullptr && cur.nb * 64 >= a.y2_c0 && cur.nb * 64 < a.y2_c0 + a.y2_cw;
     // ---- round 4: the common case (a whole 64-channel block inside the written width, no second output, no split-K slab) goes out
     //      through a per-wave transposition in LDS.  Straight from the accumulators a store instruction covered 16 pixel rows x 64
     //      bytes -- 16 partial lines per instruction, 11.7 k cycles of store issue per item with a partner on the CU
@@ -482,7 +455,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
     //      contiguous for fp32; consecutive pixels of a tile row are consecutive in memory), and the statistics need two cross-lane
     //      steps per value instead of four DPP steps per accumulator register.  Scratch: 16 rows of 272 bytes per wave in halo
     //      buffer 1 (free until the next item's second chunk), private to the wave: no barrier.
-    const bool fast = !BNRED && !raw && full && !to_y2 && V3_FAST_EPILOGUE;
+    const bool fast = !raw && full && !to_y2 && V3_FAST_EPILOGUE;
     if (fast) {
       // (the lane-derived LDS addresses of this block are recomputed per item from an opaque copy of the lane id: hoisted out of the
       //  persistent loop by hipcc they stayed live across the main loop -- 8 registers it does not have)
@@ -652,7 +625,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
       // (written above)
     } else if (to_y2 && a.y2_only) {
       // (this block of the result exists as bf16 rows only)
-    } else if (!BNRED && !raw && a.y16) {
+    } else if (!raw && a.y16) {
       // bf16 output: a lane's four channels are one 8-byte store (round-to-nearest-even, v_cvt_pk_bf16_f32)
       h16_t* d16 = reinterpret_cast<h16_t*>(a.y);
 #pragma unroll
@@ -669,7 +642,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
             }
         }
       }
-    } else if (!BNRED && !raw && a.accumulate) {
+    } else if (!raw && a.accumulate) {
       if (full) { V3_STORE_LOOP(true, true) } else { V3_STORE_LOOP(true, nlane + nt * 16 < dcw) }
     } else {
       if (full) { V3_STORE_LOOP(false, true) } else { V3_STORE_LOOP(false, nlane + nt * 16 < dcw) }
@@ -678,7 +651,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
 #ifdef HPRI_STAMPS
     if (ntiles_done == 0) { V3_STAMP(2) }
 #endif
-    if (!fast && !BNRED && !raw && a.stats != nullptr) {
+    if (!fast && !raw && a.stats != nullptr) {
       // per-tile, per-channel (mean, M2, count): each wave makes an exact two-pass record of its own 64 pixels (sum, then
       // squared deviations from its own mean); the four wave records of a channel are merged with Chan's update after one
       // barrier.  (raw barriers: __syncthreads() would also wait for the output stores above.)
@@ -727,45 +700,6 @@ __global__ __launch_bounds__(256, 2) void conv_bf16v3_kernel(ConvV3Args a) {
         a.stats[(size_t)cur.bx * a.Cout_pad + cur.nb * 64 + tid] = make_float4(mean, m2, n, 0.f);
       }
       // (the scratch is rewritten only after the next item's main loop, i.e. behind many barriers)
-    }
-    if (BNRED) {
-      // scratch in halo buffer 1 behind the statistics': [64] parameter quads, then [4 waves][2 sums][64 channels]
-      float* prm = reinterpret_cast<float*>(smem + V3_A_BYTES + 4096);
-      float* red2 = prm + 256;
-      if (tid < 64) *reinterpret_cast<f32x4*>(prm + tid * 4) = prm4;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      V3_BARRIER();
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const f32x4 q = *reinterpret_cast<const f32x4*>(prm + (nt * 16 + 4 * lq + r) * 4);     // scale, shift, mean, invstd
-#pragma unroll
-          for (int mt = 0; mt < 4; ++mt) {
-            const float xf = (float)xq[mt][nt][r];
-            const bool keep = ((vmask >> mt) & 1u) && (!a.bn_relu || (xf * q[0] + q[1] > 0.f));
-            const float gj = keep ? acc[mt][nt][r] : 0.f;
-            t1[r] += gj;
-            t2[r] += gj * ((xf - q[2]) * q[3]);
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { t1[r] = v3_row_sum(t1[r]); t2[r] = v3_row_sum(t2[r]); }
-        if (li == 0) {
-          *reinterpret_cast<f32x4*>(red2 + (wave * 2 + 0) * 64 + nt * 16 + 4 * lq) = t1;
-          *reinterpret_cast<f32x4*>(red2 + (wave * 2 + 1) * 64 + nt * 16 + 4 * lq) = t2;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      V3_BARRIER();
-      if (tid < 128) {                           // (sum, channel) = (tid >> 6, tid & 63): the four wave records in a fixed order
-        const int which = tid >> 6, c = tid & 63;
-        float tsum = 0.f;
-#pragma unroll
-        for (int w2 = 0; w2 < 4; ++w2) tsum += red2[(w2 * 2 + which) * 64 + c];
-        if (cur.nb * 64 + c < a.bn_cpart) a.bn_part[((size_t)cur.bx * 2 + which) * a.bn_cpart + cur.nb * 64 + c] = tsum;
-      }
     }
 #ifdef HPRI_STAMPS
     if (ntiles_done == 0) { V3_STAMP(3) }
@@ -849,7 +783,7 @@ static V3Segs v3_segments(int H, int W) {
   return best;
 }
 
-// Split-K (host only), priced as in conv_bf16v2.hip: a slice costs 2 k output sizes of fp32 slab traffic against the partial
+// Split-K (host only), priced by its traffic: a slice costs 2 k output sizes of fp32 slab traffic against the partial
 // round of workgroup slots (two per CU) it fills; only problems below half a round are cut.
 static int v3_ksplit(int N, int H, int W, int Cin_pad, int Cout_pad) {
   const int ncu = hpri_cu_count();
@@ -886,14 +820,11 @@ extern "C" int hpri_splitk_finish(const float* ws, int ksplit, int Cout_pad, con
 #define V3_STAGGER_CYCLES 6000      // about one store + statistics epilogue with a partner on the CU
 
 struct V3Out2 { void* y2; int cs, coff, c0, cw, only; };
-struct V3BnRed {
-  const void* x16; int x_cs, x_coff; const float *mean, *invstd, *scale, *shift; int relu; float* part; int cpart;
-};
 
 static int v3_launch(const void* xp, long long x_plane, int x_cs, int x_coff, const void* wp, const float* bias,
                      float* y, int y_cs, int y_coff, float* stats, int N, int H, int W, int Cin_pad, int Cout,
                      int Cout_pad, int y_cw, int accumulate, int split, float* ws, size_t ws_floats,
-                     unsigned long long* stamps, int stagger_cycles, const V3BnRed* bn, hipStream_t stream,
+                     unsigned long long* stamps, int stagger_cycles, hipStream_t stream,
                      const V3Out2* o2 = nullptr) {
   HPRI_REQUIRE(xp && wp && y, "conv_bf16v3: null pointer");
   HPRI_REQUIRE(N > 0 && H > 0 && W > 0, "conv_bf16v3: empty image");
@@ -949,66 +880,29 @@ static int v3_launch(const void* xp, long long x_plane, int x_cs, int x_coff, co
   dim3 grid((unsigned)(nloc * 8), 1u, (unsigned)a.ksplit);
   a.y2 = nullptr; a.y2_cs = a.y2_coff = a.y2_c0 = a.y2_cw = a.y2_only = 0;
   if (o2 != nullptr) {
-    HPRI_REQUIRE(o2->y2 != nullptr && bn == nullptr && a.ksplit == 1 && !a.accumulate,
+    HPRI_REQUIRE(o2->y2 != nullptr && a.ksplit == 1 && !a.accumulate,
                  "conv_bf16v3_y2: the second output is not for split-K problems (hpri_conv_bf16v3_plan) or accumulating launches");
     HPRI_REQUIRE(o2->c0 % 64 == 0 && o2->cw % 64 == 0 && o2->cw > 0 && o2->c0 + o2->cw <= Cout_pad, "conv_bf16v3_y2: the channel range must be whole 64-channel blocks");
     HPRI_REQUIRE(o2->cs % 4 == 0 && o2->coff % 4 == 0 && o2->coff + o2->cw <= o2->cs && ((uintptr_t)o2->y2 & 7) == 0,
                  "conv_bf16v3_y2: the bf16 view must be 8-byte aligned and hold the channel range");
     a.y2 = reinterpret_cast<h16_t*>(o2->y2); a.y2_cs = o2->cs; a.y2_coff = o2->coff; a.y2_c0 = o2->c0; a.y2_cw = o2->cw; a.y2_only = o2->only;
   }
-  a.bn_part = nullptr;
-  if (bn != nullptr) {
-    HPRI_REQUIRE(bn->x16 && bn->mean && bn->invstd && bn->scale && bn->shift && bn->part, "conv_bf16v3_bnred: null pointer");
-    HPRI_REQUIRE(a.ksplit == 1 && !a.accumulate && !a.y16 && stats == nullptr,
-                 "conv_bf16v3_bnred: not for split-K problems (hpri_conv_bf16v3_plan), accumulating launches, bf16 outputs or launches that record statistics");
-    HPRI_REQUIRE(bn->x_cs % 4 == 0 && bn->x_coff % 4 == 0 && ((uintptr_t)bn->x16 & 7) == 0 && bn->x_cs - bn->x_coff >= 4,
-                 "conv_bf16v3_bnred: the pre-BN view must be 8-byte aligned (stride and offset multiples of 4)");
-    HPRI_REQUIRE(bn->x_cs - bn->x_coff >= ((Cout + 3) & ~3) && bn->cpart >= Cout, "conv_bf16v3_bnred: pre-BN view / partial rows narrower than the channels");
-    a.bn_x = reinterpret_cast<const h16_t*>(bn->x16); a.bn_x_cs = bn->x_cs; a.bn_x_coff = bn->x_coff;
-    a.bn_cw = (bn->x_cs - bn->x_coff) & ~3;
-    a.bn_mean = bn->mean; a.bn_invstd = bn->invstd; a.bn_scale = bn->scale; a.bn_shift = bn->shift;
-    a.bn_relu = bn->relu; a.bn_part = bn->part; a.bn_cpart = bn->cpart;
-#ifdef HPRI_DIAG_KERNELS
-    if (a.ksplit <= HPRI_Q_SLICES && a.per_xcd >= 2 * nloc) { const HpriQueueHalves qh = hpri_item_queue_take(stream); a.queue = qh.use; a.queue_clear = qh.clear; }
-    hipLaunchKernelGGL(conv_bf16v3_kernel<true>, grid, dim3(256), 0, stream, a);
-#else
-    return hpri_set_error(HPRI_ERR_UNSUPPORTED, "conv_bf16v3_bnred: diagnostics build only (HPRI_DIAG=1 python -m hyperpri_amd.build)");
-#endif
-  } else {
-    if (a.ksplit <= HPRI_Q_SLICES && a.per_xcd >= 2 * nloc) { const HpriQueueHalves qh = hpri_item_queue_take(stream); a.queue = qh.use; a.queue_clear = qh.clear; }
-    hipLaunchKernelGGL(conv_bf16v3_kernel<false>, grid, dim3(256), 0, stream, a);
-  }
+  if (a.ksplit <= HPRI_Q_SLICES && a.per_xcd >= 2 * nloc) { const HpriQueueHalves qh = hpri_item_queue_take(stream); a.queue = qh.use; a.queue_clear = qh.clear; }
+  hipLaunchKernelGGL(conv_bf16v3_kernel, grid, dim3(256), 0, stream, a);
   HPRI_CHECK_LAUNCH();
   if (a.ksplit == 1) return HPRI_OK;
   return hpri_splitk_finish(ws, a.ksplit, Cout_pad, bias, y, y_cs, y_coff, stats, N, H * W, Cout, a.y_cw, accumulate & 1, a.relu, stream);
 }
 
-#ifdef HPRI_DIAG_KERNELS   // (stagger and stamp buffer given by the caller: tools/v3_bench.py, tools/v3_stamps.py)
+#ifdef HPRI_STAMPS   // stamp builds (tools/build_v3_diag.sh) only: stagger and stamp buffer given by the caller (tools/v3_stamps.py)
 extern "C" int hpri_conv_bf16v3_dbg(const void* xp, long long x_plane, int x_cs, int x_coff, const void* wp, const float* bias,
                                     float* y, int y_cs, int y_coff, float* stats, int N, int H, int W, int Cin_pad, int Cout,
                                     int Cout_pad, int y_cw, int accumulate, int split, float* ws, size_t ws_floats,
                                     unsigned long long* stamps, int stagger_cycles, hipStream_t stream) {
   return v3_launch(xp, x_plane, x_cs, x_coff, wp, bias, y, y_cs, y_coff, stats, N, H, W, Cin_pad, Cout, Cout_pad, y_cw, accumulate,
-                   split, ws, ws_floats, stamps, stagger_cycles, nullptr, stream);
+                   split, ws, ws_floats, stamps, stagger_cycles, stream);
 }
-#endif   // HPRI_DIAG_KERNELS
-
-#ifdef HPRI_DIAG_KERNELS   // measured neutral to -3 % in round 3: kept for A/B in the diagnostics build only
-// The data gradient of a 3x3 layer whose input x = ReLU(BN(bn_x16)) has no other consumer, with that BatchNorm's backward
-// reduction taken in the epilogue (the bf16-mode counterpart of hpri_conv_wino4_bnred): bn_x16 = the pre-BN tensor as bf16 (same
-// pixels as y; bn_x_cs / bn_x_coff in elements), its per-channel mean / invstd / scale / shift, bn_relu; bn_part[stat tiles][2][bn_cpart]
-// (stat tiles: hpri_conv_bf16v3_plan, which must report ksplit 1) receives sum g*[y>0] and sum g*[y>0]*xhat per tile.  Finish with
-// hpri_bn_relu_bwd_fused.
-extern "C" int hpri_conv_bf16v3_bnred(const void* xp, int x_cs, int x_coff, const void* wp, float* y, int y_cs, int y_coff, int N, int H,
-                                      int W, int Cin_pad, int Cout, int Cout_pad, int y_cw, const void* bn_x16, int bn_x_cs,
-                                      int bn_x_coff, const float* bn_mean, const float* bn_invstd, const float* bn_scale,
-                                      const float* bn_shift, int bn_relu, float* bn_part, int bn_cpart, hipStream_t stream) {
-  const V3BnRed bn{bn_x16, bn_x_cs, bn_x_coff, bn_mean, bn_invstd, bn_scale, bn_shift, bn_relu, bn_part, bn_cpart};
-  return v3_launch(xp, 0, x_cs, x_coff, wp, nullptr, y, y_cs, y_coff, nullptr, N, H, W, Cin_pad, Cout, Cout_pad, y_cw, 0, 0, nullptr, 0,
-                   nullptr, V3_STAGGER_CYCLES, &bn, stream);
-}
-
-#endif   // HPRI_DIAG_KERNELS
+#endif   // HPRI_STAMPS
 
 // hpri_conv_bf16v3 (no accumulate, no split-K) whose result channels [c0, c0 + cw) -- whole 64-channel blocks -- are also
 // (y2_only != 0: only) written as bf16 rows: y2 + pixel * y2_cs + y2_coff + (channel - c0).  The data gradient of the first
@@ -1021,15 +915,19 @@ extern "C" int hpri_conv_bf16v3_y2(const void* xp, int x_cs, int x_coff, const v
   // elements; the gradient of a planes-only skip tensor: its readers -- pooling backward, BatchNorm backward -- read bf16)
   const V3Out2 o2{y2, y2_cs, y2_coff, y2_c0, y2_cw, y2_only & 1};
   return v3_launch(xp, 0, x_cs, x_coff, wp, bias, y, y_cs, y_coff, stats, N, H, W, Cin_pad, Cout, Cout_pad, y_cw, (y2_only & 2) ? 4 : 0, 0,
-                   nullptr, 0, nullptr, V3_STAGGER_CYCLES, nullptr, stream, &o2);
+                   nullptr, 0, nullptr, V3_STAGGER_CYCLES, stream, &o2);
 }
 
-// 3x3 pad-1 convolution (forward, or data gradient with the flipped pack) over bf16 activation planes: same argument
-// contract as hpri_conv_bf16v2 (x_plane is unused: one plane); statistics records per 256-pixel tile (hpri_conv_bf16v3_plan).
+// 3x3 pad-1 convolution (forward, or data gradient with the flipped pack) over bf16 activation planes.  xp: one plane of x_cs
+// elements per pixel, channels [x_coff, x_coff + Cin_pad) (x_plane is unused, split must be 0); wp from hpri_pack_weight_bf16; bias
+// may be null.  accumulate bit 0: y += result, bit 1: ReLU, bit 2: y is a bf16 view (y_cs / y_coff in elements; not with bit 0, not for
+// split-K problems).  y_cw = channels written per pixel (at least Cout; the view float4-aligned).  stats (may be null): one (mean, M2,
+// count, 0) record per 256-pixel tile and channel, [stat_tiles][Cout_pad]; ws / ws_floats: the split-K slabs when
+// hpri_conv_bf16v3_plan reports ksplit > 1 (finished by hpri_splitk_finish: records per 64 pixels then).
 extern "C" int hpri_conv_bf16v3(const void* xp, long long x_plane, int x_cs, int x_coff, const void* wp, const float* bias,
                                 float* y, int y_cs, int y_coff, float* stats, int N, int H, int W, int Cin_pad, int Cout,
                                 int Cout_pad, int y_cw, int accumulate, int split, float* ws, size_t ws_floats,
                                 hipStream_t stream) {
   return v3_launch(xp, x_plane, x_cs, x_coff, wp, bias, y, y_cs, y_coff, stats, N, H, W, Cin_pad, Cout, Cout_pad, y_cw, accumulate,
-                   split, ws, ws_floats, nullptr, V3_STAGGER_CYCLES, nullptr, stream);
+                   split, ws, ws_floats, nullptr, V3_STAGGER_CYCLES, stream);
 }

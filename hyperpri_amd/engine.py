@@ -316,7 +316,7 @@ class Act:
 class Planes:
     """bf16 NHWC planes of an activation: plane p (0 = bf16(x), 1 = bf16(x - hi), ...) starts ``plane`` elements after
     the previous one, ``cs`` elements per pixel (a multiple of 32), channels [C, cs) are zero.  In the bf16 precision
-    modes the 3x3 convolutions bring their operands into LDS by DMA straight from these planes (csrc/conv_bf16v2.hip)."""
+    modes the 3x3 convolutions bring their operands into LDS by DMA straight from these planes (csrc/conv_bf16v3.hip)."""
     __slots__ = ("buf", "plane", "cs", "coff", "npl", "cw")
 
     def __init__(self, buf: torch.Tensor, plane: int, cs: int, coff: int, npl: int, cw: int = 0):

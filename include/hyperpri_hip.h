@@ -135,8 +135,7 @@ int hpri_conv_fwd(const float* x, int x_cs, int x_coff, const float* wp, const f
  * transforms the filters (U = G g G^T; mode 0 forward, mode 1 data gradient, optional per-column scale for the eval-mode BN
  * fold) into [K/8][16][Ncols_pad][8] (hpri_wino_packed_floats floats); hpri_conv_wino4_plan gives the number of BatchNorm partial
  * records (one per 16 x 8-pixel tile); `accumulate` bit 0: y += result, bit 1: ReLU.  x: fp32 NHWC view with channels
- * [Cin, Cin_pad) zero (Cin_pad a multiple of 8).  (The first form of this kernel, conv_wino.hip, lives in the diagnostics build:
- * hyperpri_hip_diag.h.) */
+ * [Cin, Cin_pad) zero (Cin_pad a multiple of 8).  (conv_wino.hip holds the weight gradient of the same transform, below.) */
 size_t hpri_wino_packed_floats(int K, int Ncols_pad);
 int hpri_wino4_pack(const float* w, float* up, const float* colscale, int mode, int K, int Ncols, int Ncols_pad, int src_d1,
                     hipStream_t stream);
@@ -224,8 +223,8 @@ int hpri_conv3x3_ingest_h16(const float* x, const void* wp, const float* bias, v
  * x_plane is unused (one plane); `split` must be 0; `accumulate` bit 0: y += result, bit 1: ReLU; plan / workspace / statistics
  * contract as hpri_conv_fwd (records per 256-pixel tile: hpri_conv_bf16v3_plan); the output view must be float4-aligned.  Bit 2 of `accumulate` (value 4): the output view is bf16 (y points at bf16 elements,
  * y_cs / y_coff in elements; not with bit 0, not for split-K problems) -- the pre-BN tensor at 2 bytes per element, read by
- * hpri_bn_apply_relu_x16 / hpri_bn_relu_bwd_x16.  (Its predecessor conv_bf16v2.hip, the _dbg entry with a caller-given stagger and stamp
- * buffer, and the variant with BatchNorm-backward sums in the epilogue live in the diagnostics build: hyperpri_hip_diag.h.) */
+ * hpri_bn_apply_relu_x16 / hpri_bn_relu_bwd_x16.  (Stamp builds, -DHPRI_STAMPS by tools/build_v3_diag.sh, add an undeclared
+ * hpri_conv_bf16v3_dbg with a caller-given stagger and stamp buffer; the product libraries do not export it.) */
 int hpri_conv_bf16v3_plan(int N, int H, int W, int Cin_pad, int Cout_pad, int* ksplit, int* stat_tiles,
                           size_t* ws_floats);
 int hpri_conv_bf16v3(const void* xp, long long x_plane, int x_cs, int x_coff, const void* wp, const float* bias, float* y,

@@ -20,6 +20,24 @@ def test_exports_every_declared_symbol():
     assert lib.hpri_version() >= 100
 
 
+def test_exports_no_undeclared_symbol():
+    """The boundary in the other direction: every dynamic symbol beginning ``hpri_`` that the two product libraries define is
+    declared in include/hyperpri_hip.h.  There is no second header: an undeclared export is a leftover."""
+    import subprocess
+    import sys
+    from hyperpri_amd import _lib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import check_codeobj
+    _lib.load()
+    declared = set(_lib.parse_header())
+    for path in (_lib.LIB_PATH, _lib.LIB_F16_PATH):
+        out = subprocess.run([check_codeobj._readelf(), "--dyn-syms", "-W", path], capture_output=True, text=True, check=True).stdout
+        rows = [ln.split() for ln in out.splitlines()]          # Num: Value Size Type Bind Vis Ndx Name
+        exported = {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].endswith(":") and r[6] != "UND" and r[7].startswith("hpri_")}
+        assert len(exported) > 100, (path, len(exported))       # the table was really read
+        assert exported <= declared, (path, sorted(exported - declared))
+
+
 def test_bad_arguments_are_rejected_without_launch():
     from hyperpri_amd import _lib
     lib = _lib.load()

@@ -97,7 +97,7 @@ def test_documented_switches_are_twelve_and_all_known():
     assert set(SWITCHES) <= doc, sorted(set(SWITCHES) - doc)
     # ... and every HPRI_* variable the package reads is a documented one (bench / test harness variables aside)
     src = "".join(open(os.path.join(root, "hyperpri_amd", f)).read() for f in os.listdir(os.path.join(root, "hyperpri_amd")) if f.endswith(".py"))
-    read = set(re.findall(r"environ(?:\.get|\.setdefault)?\(?\[?\"(HPRI_[A-Z0-9_]+)\"", src)) - {"HPRI_DIAG"}
+    read = set(re.findall(r"environ(?:\.get|\.setdefault)?\(?\[?\"(HPRI_[A-Z0-9_]+)\"", src))
     assert read <= doc, sorted(read - doc)
 
 

@@ -33,7 +33,7 @@ sys.path.insert(0, ROOT)
 from hyperpri_amd import build as B  # noqa: E402
 
 # Kernels a training / predict step of the BASELINE configs launches (demangled-name prefixes): these must hold every value in
-# registers.  Anything else in the library (diagnostic entry points, superseded forms kept for A/B) is reported, not gated.
+# registers.  Anything else in the library is reported, not gated.
 HOT = (
     "conv_wino4_kernel", "conv_wino_wgrad_kernel", "wino_wgrad_reduce_kernel", "wino_wgrad_reduce_wide_kernel",
     "conv_bf16v3_kernel", "conv_wgrad_bf16v2_kernel", "gemm_bf16v3_kernel", "gemm_f32v2_kernel", "wgrad1x1_bf16v3_kernel",

@@ -2,8 +2,6 @@
 """Is the bf16 plane convolution limited by the chip's power management?  The same launch (238->64, 608x968, batch 2) on
 all-zero operands (no switching activity in the matrix pipe, LDS and DMA data paths) and on random operands: the instruction
 stream and the memory traffic are identical, only the data -- and with it the power draw and the clock the chip holds -- differ."""
-import os as _os
-_os.environ.setdefault("HPRI_DIAG", "1")     # uses entry points of the DIAGNOSTICS build (include/hyperpri_hip_diag.h): HPRI_DIAG=1 python -m hyperpri_amd.build
 import ctypes
 import json
 import os
@@ -31,10 +29,10 @@ for name in ("zeros", "random", "zeros", "random"):
     b = torch.zeros(COUT, device=dev)
     y = torch.empty(N * H * W * COUT, device=dev)
     k, tl, wsf = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
-    lib.hpri_conv_bf16v2_plan(N, H, W, cs16, cout_pad, ctypes.byref(k), ctypes.byref(tl), ctypes.byref(wsf))
+    lib.hpri_conv_bf16v3_plan(N, H, W, cs16, cout_pad, ctypes.byref(k), ctypes.byref(tl), ctypes.byref(wsf))
     stats = torch.empty(tl.value * cout_pad * 4, device=dev)
     ws = torch.empty(max(wsf.value, 4), device=dev)
-    call = lambda: lib.hpri_conv_bf16v2(P(planes), 0, cs16, 0, P(wp), P(b), P(y), COUT, 0, P(stats), N, H, W, cs16, COUT, cout_pad, COUT, 0, 0,
+    call = lambda: lib.hpri_conv_bf16v3(P(planes), 0, cs16, 0, P(wp), P(b), P(y), COUT, 0, P(stats), N, H, W, cs16, COUT, cout_pad, COUT, 0, 0,
                                         P(ws), ws.numel(), st)
     for _ in range(20):
         assert call() == 0

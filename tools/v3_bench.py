@@ -1,10 +1,8 @@
 #!/usr/bin/env python3
-"""A/B of the two bf16-PLANE 3x3 convolutions on the CubeNET layer shapes: conv_bf16v2.hip (one persistent 8-wave workgroup per
-CU, 32x32x16 MFMA) against conv_bf16v3.hip (two 4-wave workgroups per CU, 16x16x32 MFMA, stores from the accumulators).
-Interleaved rounds in one process on the same random data (rule 24); outputs and BN partial statistics compared.
-    usage: v3_bench.py [out.json]      env: SHAPES='[[N,H,W,Cin,Cout],...]'  STAGGER='0,3000,6000' (extra v3 arms via _dbg)"""
-import os as _os
-_os.environ.setdefault("HPRI_DIAG", "1")     # uses entry points of the DIAGNOSTICS build (include/hyperpri_hip_diag.h): HPRI_DIAG=1 python -m hyperpri_amd.build
+"""The bf16-PLANE 3x3 convolution (conv_bf16v3.hip: two 4-wave workgroups per CU, 16x16x32 MFMA, stores from the accumulators) on the
+CubeNET layer shapes: interleaved rounds in one process on the same random data (rule 24), with and (NOSTATS=1) without the BatchNorm
+partial statistics; the statistics records are checked against the fp32 output they describe.
+    usage: v3_bench.py [out.json]      env: SHAPES='[[N,H,W,Cin,Cout],...]'  DATA=randn|relu|uniform01|zeros  NOSTATS=1"""
 import ctypes
 import json
 import os
@@ -20,7 +18,6 @@ SHAPES = json.loads(os.environ["SHAPES"]) if "SHAPES" in os.environ else [  # N,
     (2, 304, 484, 128, 128), (2, 304, 484, 256, 128), (2, 152, 242, 256, 256), (2, 152, 242, 512, 256),
     (2, 76, 121, 512, 512), (2, 76, 121, 1024, 512), (2, 38, 60, 1024, 1024),
 ]
-STAGGERS = [int(v) for v in os.environ.get("STAGGER", "").split(",") if v]
 
 
 def rup(x, m):
@@ -60,32 +57,17 @@ def main():
         wpb = torch.empty(((Cin + 31) // 32) * 9 * cout_pad * 32, dtype=torch.bfloat16, device=dev)
         assert lib.hpri_pack_weight_bf16(P(w), P(wpb), 0, Cin, Cout, cout_pad, 9, Cin, 0, 0, st) == 0
         arms = {}
-        for kind in ["v2", "v3"] + [f"v3s{s}" for s in STAGGERS] + (["v3nostats"] if os.environ.get("NOSTATS") else []):
-            k, tl, wsf = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
-            plan = lib.hpri_conv_bf16v2_plan if kind == "v2" else lib.hpri_conv_bf16v3_plan
-            plan(N, H, W, cs16, cout_pad, ctypes.byref(k), ctypes.byref(tl), ctypes.byref(wsf))
+        k, tl, wsf = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()
+        lib.hpri_conv_bf16v3_plan(N, H, W, cs16, cout_pad, ctypes.byref(k), ctypes.byref(tl), ctypes.byref(wsf))
+        for kind in ["v3"] + (["v3nostats"] if os.environ.get("NOSTATS") else []):
             ws = torch.empty(max(wsf.value, 4), device=dev)
             stats = torch.zeros(tl.value * cout_pad * 4, device=dev)
             y = torch.zeros(N * H * W * Cout, device=dev)
-            if kind == "v2":
-                def call(y=y, stats=stats, ws=ws):
-                    return lib.hpri_conv_bf16v2(P(planes), 0, cs16, 0, P(wpb), P(b), P(y), Cout, 0, P(stats), N, H, W, cs16, Cout,
-                                                cout_pad, Cout, 0, 0, P(ws), ws.numel(), st)
-            elif kind == "v3nostats":
-                def call(y=y, stats=stats, ws=ws):
-                    return lib.hpri_conv_bf16v3(P(planes), 0, cs16, 0, P(wpb), P(b), P(y), Cout, 0, P(None), N, H, W, cs16, Cout,
-                                                cout_pad, Cout, 0, 0, P(ws), ws.numel(), st)
-            elif kind == "v3":
-                def call(y=y, stats=stats, ws=ws):
-                    return lib.hpri_conv_bf16v3(P(planes), 0, cs16, 0, P(wpb), P(b), P(y), Cout, 0, P(stats), N, H, W, cs16, Cout,
-                                                cout_pad, Cout, 0, 0, P(ws), ws.numel(), st)
-            else:
-                sg = int(kind[3:])
 
-                def call(y=y, stats=stats, ws=ws, sg=sg):
-                    return lib.hpri_conv_bf16v3_dbg(P(planes), 0, cs16, 0, P(wpb), P(b), P(y), Cout, 0, P(stats), N, H, W, cs16, Cout,
-                                                    cout_pad, Cout, 0, 0, P(ws), ws.numel(), P(None), sg, st)
-            arms[kind] = (call, y, stats, k.value, tl.value)
+            def call(y=y, stats=stats if kind == "v3" else None, ws=ws):
+                return lib.hpri_conv_bf16v3(P(planes), 0, cs16, 0, P(wpb), P(b), P(y), Cout, 0, P(stats), N, H, W, cs16, Cout,
+                                            cout_pad, Cout, 0, 0, P(ws), ws.numel(), st)
+            arms[kind] = (call, y, stats)
         res = {k: [] for k in arms}
         for rnd in range(6):
             for kind, (fn, *_r) in arms.items():
@@ -99,19 +81,16 @@ def main():
                 torch.cuda.synchronize()
                 if rnd > 0:
                     res[kind].append(e0.elapsed_time(e1) / reps)
-        y2, y3 = arms["v2"][1], arms["v3"][1]
-        m2, v2 = chan_stats(arms["v2"][2], arms["v2"][4], cout_pad, Cout)
-        m3, v3 = chan_stats(arms["v3"][2], arms["v3"][4], cout_pad, Cout)
-        med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-        row = {"shape": [N, H, W, Cin, Cout], "ms": med, "tf": {k: flops / v / 1e9 for k, v in med.items()},
-               "ksplit": {k: arms[k][3] for k in arms}, "max_abs_dy": float((y2 - y3).abs().max()),
-               "max_abs_y": float(y2.abs().max()), "max_dmean": float((m2 - m3).abs().max()),
-               "max_dvar_rel": float(((v2 - v3).abs() / v2).max())}
+        y3 = arms["v3"][1].view(N * H * W, Cout).double()
+        m3, v3 = chan_stats(arms["v3"][2], tl.value, cout_pad, Cout)
+        med = {kd: sorted(v)[len(v) // 2] for kd, v in res.items()}
+        row = {"shape": [N, H, W, Cin, Cout], "ms": med, "tf": {kd: flops / v / 1e9 for kd, v in med.items()}, "ksplit": k.value,
+               "max_abs_y": float(y3.abs().max()), "max_dmean": float((m3 - y3.mean(0)).abs().max()),
+               "max_dvar_rel": float(((v3 - y3.var(0, unbiased=False)).abs() / y3.var(0, unbiased=False)).max())}
         rows.append(row)
-        print(f"N{N} {H}x{W} {Cin}->{Cout}: " + "  ".join(f"{k} {row['tf'][k]:7.1f} TF ({med[k]:.3f} ms, k{row['ksplit'][k]})" for k in med)
-              + f"  max|dy| {row['max_abs_dy']:.2e} of {row['max_abs_y']:.1f}  dmean {row['max_dmean']:.1e} dvar {row['max_dvar_rel']:.1e}",
-              flush=True)
-        del planes, arms, y2, y3
+        print(f"N{N} {H}x{W} {Cin}->{Cout} (k{k.value}): " + "  ".join(f"{kd} {row['tf'][kd]:7.1f} TF ({med[kd]:.3f} ms)" for kd in med)
+              + f"  max|y| {row['max_abs_y']:.1f}  statistics vs output: dmean {row['max_dmean']:.1e} dvar {row['max_dvar_rel']:.1e}", flush=True)
+        del planes, arms, y3
         torch.cuda.empty_cache()
     if len(sys.argv) > 1:
         with open(sys.argv[1], "w") as f:

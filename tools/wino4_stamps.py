@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
-"""Cycle shares of a conv_wino4 workgroup (4 waves, 16x8 pixels; two stamp groups = waves 0-1 / 2-3) (diagnostic build, tools/build_stamps.sh): main loop | output transform + stores |
+"""Cycle shares of a conv_wino4 workgroup (4 waves, 16x8 pixels; two stamp groups = waves 0-1 / 2-3) (diagnostic build, tools/build_wino4_diag.sh): main loop | output transform + stores |
 statistics, median over workgroups."""
-import os as _os
-_os.environ.setdefault("HPRI_DIAG", "1")     # uses entry points of the DIAGNOSTICS build (include/hyperpri_hip_diag.h): HPRI_DIAG=1 python -m hyperpri_amd.build
 import ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -11,7 +9,7 @@ SHAPES = [(2, 608, 968, 238, 64), (2, 304, 484, 128, 128)]
 if os.environ.get("WINO_SHAPES"):      # e.g. "2,608,968,64,64;2,304,484,128,128"
     SHAPES = [tuple(int(v) for v in q.split(",")) for q in os.environ["WINO_SHAPES"].split(";")]
 def rup(x, m): return (x + m - 1) // m * m
-LIBNAME = os.environ.get("WINO_LIB", "libv2stamps.so")
+LIBNAME = os.environ.get("WINO_LIB", "libwino4diag0.so")
 print("library", LIBNAME)
 lib = ctypes.CDLL(os.path.join(ROOT, "hyperpri_amd", "lib", LIBNAME))
 lib.hpri_last_error.restype = ctypes.c_char_p
