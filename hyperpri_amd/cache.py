@@ -47,11 +47,33 @@ been requested.  What orders the gather that overwrites a buffer behind the step
     out on.  There the cache waits as ``CubeStager.submit()`` does: for the event ``release()`` recorded (``_consumed``)
     or, without one, for everything enqueued so far on that earlier stream.
 Requesting batch k + out_slots BEFORE the backward of batch k has been enqueued is outside this contract.
+
+Augmentation (``CubeAugment``, ``plan_epoch_augmented``, csrc/cache_warp.hip) -- opt-in; without it nothing above changes.
+A sample that asks for more than a crop and flips is served by the warp kernel pair: the window is resampled through one
+affine map (bilinear for the cube, nearest neighbour for the mask), scaled by ``gain``, shifted by ``offset`` and a run of
+bands is zeroed.  Per sample one 64-byte entry of 16 32-bit words:
+    ``[slot, drop_lo, drop_n, 0, a00, a01, cx, a10, a11, cy, gain, offset, 0, 0, 0, 0]``  (words 4..11 hold fp32 bits)
+    output pixel (y, x):  u = x - (w-1)/2, v = y - (h-1)/2;  source column sx = a00 u + a01 v + cx, row sy = a10 u + a11 v + cy
+    A = (1/zoom) [[cos t, -sin t], [sin t, cos t]], column 0 negated by a column flip, column 1 by a row flip (fp64, rounded
+    once to fp32; multiples of 90 degrees use exact 0 / +-1); cx = left + (w-1)/2 + shift_x, cy = top + (h-1)/2 + shift_y.
+Draw order of ``plan_epoch_augmented``: first ``plan_epoch``'s draws, unchanged; then ten vectors
+``torch.rand(n, dtype=torch.float64, generator=g)``, ALL of them whatever the settings are (a knob never shifts another
+quantity's stream), entry j again for the j-th sample served:
+  1. ``apply``: the sample is warped geometrically when ``apply < p``  (else angle 0, zoom 1, no shift);
+  2. ``angle = (2 r - 1) * rotate`` degrees;
+  3. ``zoom = exp(log(lo) + r * (log(hi) - log(lo)))``  (above 1 magnifies: the source step is 1 / zoom);
+  4. ``shift_x = (2 r - 1) * shift``;   5. ``shift_y`` likewise;
+  6. ``gain = lo + r * (hi - lo)``;     7. ``offset`` likewise  (both for every sample, warped or not);
+  8. ``drop``: a run of bands is dropped when ``drop < probability``;
+  9. ``run = min(1 + floor(r * max_run), max_run, C)``;   10. ``drop_lo = min(floor(r * (C - run + 1)), C - run)``.
+A batch in which no sample needs the warp (identity geometry, gain 1, offset 0, no drop) goes through the plain gather.
 """
 from __future__ import annotations
 
 import ctypes
 import logging
+import math
+from dataclasses import dataclass
 from typing import Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -104,6 +126,125 @@ def plan_epoch(n: int, batch_size: int, frame: Tuple[int, int], patch=None, shuf
     table = torch.stack([order, top, left, fh + 2 * fw], dim=1)[:m].to(torch.int32).contiguous()
     batches = [(s, min(s + batch_size, m)) for s in range(0, m, batch_size)]
     return EpochPlan(order[:m].clone(), table, batches, (h, w))
+
+
+def _pair(v, what: str) -> Tuple[float, float]:
+    lo, hi = (v, v) if isinstance(v, (int, float)) else v
+    lo, hi = float(lo), float(hi)
+    if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+        raise ValueError(f"CubeAugment: {what} must be a finite (lo, hi) range with lo <= hi, got {v!r}")
+    return lo, hi
+
+
+@dataclass(frozen=True)
+class CubeAugment:
+    """What ``plan_epoch_augmented`` draws per sample (module docstring); the defaults are neutral.  Needs no device."""
+    p: float = 0.0                                  # probability that a sample is warped geometrically at all
+    rotate: float = 0.0                             # degrees: the angle is uniform in [-rotate, rotate]
+    zoom: Tuple[float, float] = (1.0, 1.0)          # (lo, hi), log-uniform; above 1 magnifies
+    shift: float = 0.0                              # pixels: the window centre moves uniformly in [-shift, shift] per axis
+    gain: Tuple[float, float] = (1.0, 1.0)          # (lo, hi), uniform
+    offset: Tuple[float, float] = (0.0, 0.0)        # (lo, hi), uniform
+    band_drop: Tuple[float, int] = (0.0, 1)         # (probability, longest run of bands set to zero)
+
+    def __post_init__(self):
+        for name in ("p", "rotate", "shift"):
+            v = float(getattr(self, name))
+            if not math.isfinite(v):
+                raise ValueError(f"CubeAugment: {name} must be finite, got {v!r}")
+            object.__setattr__(self, name, v)
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError(f"CubeAugment: p must lie in [0, 1], got {self.p!r}")
+        if self.rotate < 0 or self.shift < 0:
+            raise ValueError("CubeAugment: rotate and shift are half-widths and must not be negative")
+        z = _pair(self.zoom, "zoom")
+        if z[0] <= 0 or z[0] < 1 / 16 or z[1] > 16:
+            raise ValueError(f"CubeAugment: zoom must lie in [1/16, 16], got {self.zoom!r}")
+        object.__setattr__(self, "zoom", z)
+        object.__setattr__(self, "gain", _pair(self.gain, "gain"))
+        object.__setattr__(self, "offset", _pair(self.offset, "offset"))
+        prob, run = self.band_drop
+        prob = float(prob)
+        if not (math.isfinite(prob) and 0.0 <= prob <= 1.0):
+            raise ValueError(f"CubeAugment: the band_drop probability must lie in [0, 1], got {prob!r}")
+        if isinstance(run, float) and not run.is_integer() or int(run) < 1:
+            raise ValueError(f"CubeAugment: the band_drop run must be a whole number of at least 1, got {run!r}")
+        object.__setattr__(self, "band_drop", (prob, int(run)))
+
+
+def warp_matrix(angle: float, zoom: float, flip_h: bool, flip_w: bool) -> Tuple[float, float, float, float]:
+    """``(a00, a01, a10, a11)`` in fp64: (1/zoom) * rotation by ``angle`` degrees, column 0 negated by a column flip and
+    column 1 by a row flip.  Multiples of 90 degrees use exact 0 and +-1."""
+    k = angle / 90.0
+    if k == math.floor(k):
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(k) % 4]
+    else:
+        c, s = math.cos(math.radians(angle)), math.sin(math.radians(angle))
+    r = 1.0 / zoom
+    a00, a01, a10, a11 = r * c, -(r * s), r * s, r * c
+    if flip_w:
+        a00, a10 = -a00, -a10
+    if flip_h:
+        a01, a11 = -a01, -a11
+    return a00 + 0.0, a01 + 0.0, a10 + 0.0, a11 + 0.0          # (+ 0.0: no negative zeros in the table)
+
+
+def warp_entries(slots, tops, lefts, flip_h, flip_w, window, angle, zoom, shift_x, shift_y, gain, offset, drop_lo, drop_n) -> torch.Tensor:
+    """The (n, 16) int32 entry array of the warp kernels (module docstring) from per-sample sequences: fp64 arithmetic,
+    rounded once to fp32."""
+    h, w = window
+    n = len(slots)
+    f = np.zeros((n, 8), dtype=np.float64)
+    for j in range(n):
+        a00, a01, a10, a11 = warp_matrix(float(angle[j]), float(zoom[j]), bool(flip_h[j]), bool(flip_w[j]))
+        f[j] = (a00, a01, float(lefts[j]) + (w - 1) / 2 + float(shift_x[j]), a10, a11, float(tops[j]) + (h - 1) / 2 + float(shift_y[j]),
+                float(gain[j]), float(offset[j]))
+    e = np.zeros((n, 16), dtype=np.int32)
+    e[:, 0] = np.asarray(slots, dtype=np.int64)
+    e[:, 1] = np.asarray(drop_lo, dtype=np.int64)
+    e[:, 2] = np.asarray(drop_n, dtype=np.int64)
+    e[:, 4:12] = f.astype(np.float32).view(np.int32)
+    return torch.from_numpy(e)
+
+
+class AugmentedPlan(NamedTuple):
+    order: torch.Tensor                 # as EpochPlan
+    table: torch.Tensor                 # (m, 4) int32: the plain table, exactly plan_epoch's
+    entries: torch.Tensor               # (m, 16) int32: the warp entries (words 4..11 hold fp32 bits)
+    batches: List[Tuple[int, int]]
+    window: Tuple[int, int]
+    warped: List[bool]                  # per batch: some sample needs the warp kernels
+
+
+def plan_epoch_augmented(n: int, batch_size: int, frame: Tuple[int, int], channels: int, augment: Optional[CubeAugment] = None,
+                         patch=None, shuffle: bool = True, random_crop: bool = False, flips: bool = False, drop_last: bool = False,
+                         generator: Optional[torch.Generator] = None) -> AugmentedPlan:
+    """``plan_epoch`` plus the augmentation draws of the module docstring (a pure host function; ``channels`` is the band
+    count C the dropped runs lie in).  Order, windows and flips are ``plan_epoch``'s for the same generator state."""
+    if channels <= 0:
+        raise ValueError("plan_epoch_augmented: channels must be positive")
+    aug = CubeAugment() if augment is None else augment
+    plan = plan_epoch(n, batch_size, frame, patch, shuffle, random_crop, flips, drop_last, generator)
+    r = [torch.rand(n, dtype=torch.float64, generator=generator).numpy() for _ in range(10)]
+    m = plan.table.shape[0]
+    apply = r[0] < aug.p
+    angle = np.where(apply, (2 * r[1] - 1) * aug.rotate, 0.0)
+    llo, lhi = math.log(aug.zoom[0]), math.log(aug.zoom[1])
+    zoom = np.where(apply, np.exp(llo + r[2] * (lhi - llo)), 1.0)
+    sx = np.where(apply, (2 * r[3] - 1) * aug.shift, 0.0)
+    sy = np.where(apply, (2 * r[4] - 1) * aug.shift, 0.0)
+    gain = aug.gain[0] + r[5] * (aug.gain[1] - aug.gain[0])
+    offset = aug.offset[0] + r[6] * (aug.offset[1] - aug.offset[0])
+    prob, max_run = aug.band_drop
+    run = np.minimum(1 + np.floor(r[8] * max_run).astype(np.int64), min(max_run, channels))
+    drop_n = np.where(r[7] < prob, run, 0)
+    drop_lo = np.where(drop_n > 0, np.minimum(np.floor(r[9] * (channels - run + 1)).astype(np.int64), channels - run), 0)
+    t = plan.table.numpy()
+    entries = warp_entries(t[:, 0], t[:, 1], t[:, 2], t[:, 3] & 1, t[:, 3] & 2, plan.window, angle[:m], zoom[:m], sx[:m], sy[:m],
+                           gain[:m], offset[:m], drop_lo[:m], drop_n[:m])
+    needs = (angle != 0) | (zoom != 1) | (sx != 0) | (sy != 0) | (gain != 1) | (offset != 0) | (drop_n > 0)
+    warped = [bool(needs[s:e].any()) for s, e in plan.batches]
+    return AugmentedPlan(plan.order, plan.table, entries, plan.batches, plan.window, warped)
 
 
 class CubeCache:
@@ -247,6 +388,23 @@ class CubeCache:
             _lib.call("hpri_cube_gather", _p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs, tp, n,
                       h, w, _p(self._out[k]), s)
             _lib.call("hpri_mask_gather", _p(self._masks), self.capacity, self.H, self.W, tp, n, h, w, _p(self._mout[k]), s)
+        return self._hand_out(k, slots)
+
+    def _warp(self, entries_ptr: int, slots: Sequence[int], h: int, w: int) -> dict:
+        """``_gather`` through the warp kernel pair: ``entries_ptr`` points at ``len(slots)`` 64-byte entries on the device."""
+        n = len(slots)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            k = self._take_slot(n, h, w, cur)
+            s = ctypes.c_void_p(cur.cuda_stream)
+            ep = ctypes.c_void_p(entries_ptr)
+            _lib.call("hpri_cube_warp", _p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs, self.C, ep,
+                      n, h, w, _p(self._out[k]), s)
+            _lib.call("hpri_mask_warp", _p(self._masks), self.capacity, self.H, self.W, ep, n, h, w, _p(self._mout[k]), s)
+        return self._hand_out(k, slots)
+
+    def _hand_out(self, k: int, slots: Sequence[int]) -> dict:
+        n = len(slots)
         x = self._out[k][:n, :, :, :self.C].permute(0, 3, 1, 2)        # logical (N,C,h,w), channels-last strides
         if self.unsqueeze:
             x = x.unsqueeze(1)                                          # (N,1,C,h,w) as dataset.py:269-270
@@ -259,10 +417,16 @@ class CubeCache:
             if not (0 <= i < self.capacity and self._filled[i]):
                 raise IndexError(f"CubeCache: slot {i} is empty or out of range")
 
-    def batch(self, indices: Sequence[int], top=None, left=None, flip_h=None, flip_w=None, patch=None) -> dict:
+    def batch(self, indices: Sequence[int], top=None, left=None, flip_h=None, flip_w=None, patch=None, angle=None, zoom=None,
+              shift=None, gain=None, offset=None, band_drop=None, _force_warp: bool = False) -> dict:
         """``{'image', 'mask', 'index'}`` for the cached cubes ``indices``: a window of ``patch`` (the whole frame by
         default) at ``top`` / ``left`` (per sample or one value; default: centred), flipped along rows (``flip_h``) and
-        columns (``flip_w``).  Uploads a table of 16 bytes per sample; ``epoch()`` is the path without any copy."""
+        columns (``flip_w``).  Uploads a table of 16 bytes per sample; ``epoch()`` is the path without any copy.
+
+        Augmentation, each per sample or one value for all (module docstring): ``angle`` in degrees, ``zoom`` (above 1
+        magnifies), ``shift`` = ``(dx, dy)`` pixels added to the window centre, ``gain``, ``offset``, ``band_drop`` =
+        ``(first, count)`` bands written as zeros.  A batch in which every sample is neutral takes the plain gather (the
+        same bits as without these arguments); any other one the warp kernels, with 64 bytes per sample uploaded."""
         idx = [int(i) for i in indices]
         n = len(idx)
         if n == 0:
@@ -282,6 +446,32 @@ class CubeCache:
         for t_, l_ in zip(tops, lefts):
             if not (0 <= t_ <= self.H - h and 0 <= l_ <= self.W - w):
                 raise ValueError(f"CubeCache.batch: window {h}x{w} at ({t_}, {l_}) leaves the {self.H}x{self.W} frame")
+
+        def per_sample_f(v, default, width=1):
+            if v is None:
+                return [default] * n
+            a = np.asarray(v.tolist() if hasattr(v, "tolist") else v, dtype=np.float64)
+            if a.ndim == (width > 1):
+                a = np.broadcast_to(a, (n,) + a.shape)
+            if a.shape != ((n,) if width == 1 else (n, width)) or not np.isfinite(a).all():
+                raise ValueError("CubeCache.batch: one finite value per sample" if width == 1 else
+                                 f"CubeCache.batch: one finite {width}-tuple per sample")
+            return a.tolist()
+        angles, zooms, shifts = per_sample_f(angle, 0.0), per_sample_f(zoom, 1.0), per_sample_f(shift, [0.0, 0.0], 2)
+        gains, offsets, drops = per_sample_f(gain, 1.0), per_sample_f(offset, 0.0), per_sample_f(band_drop, [0.0, 0.0], 2)
+        if any(not 1 / 16 <= z <= 16 for z in zooms):
+            raise ValueError("CubeCache.batch: zoom must lie in [1/16, 16]")
+        for lo_, n_ in drops:
+            if lo_ != int(lo_) or n_ != int(n_) or lo_ < 0 or n_ < 0 or lo_ + n_ > self.C:
+                raise ValueError(f"CubeCache.batch: band_drop {(lo_, n_)} leaves the {self.C} bands")
+        neutral = all(a == 0 and z == 1 and s_ == [0.0, 0.0] and g_ == 1 and o_ == 0 and d_[1] == 0
+                      for a, z, s_, g_, o_, d_ in zip(angles, zooms, shifts, gains, offsets, drops))
+        if _force_warp or not neutral:
+            entries = warp_entries(idx, tops, lefts, fhs, fws, (h, w), angles, zooms, [s_[0] for s_ in shifts], [s_[1] for s_ in shifts],
+                                   gains, offsets, [int(d_[0]) for d_ in drops], [int(d_[1]) for d_ in drops]).to(self.device)
+            out = self._warp(entries.data_ptr(), idx, h, w)
+            entries.record_stream(torch.cuda.current_stream(self.device))
+            return out
         rows = [[i, t_, l_, (1 if a else 0) | (2 if b else 0)] for i, t_, l_, a, b in zip(idx, tops, lefts, fhs, fws)]
         table = torch.tensor(rows, dtype=torch.int32).to(self.device)
         out = self._gather(table.data_ptr(), idx, h, w)
@@ -289,27 +479,40 @@ class CubeCache:
         return out
 
     def epoch(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None, patch=None,
-              random_crop: bool = False, flips: bool = False, drop_last: bool = False) -> Iterator[dict]:
+              random_crop: bool = False, flips: bool = False, drop_last: bool = False,
+              augment: Optional[CubeAugment] = None) -> Iterator[dict]:
         """Iterate one epoch (``plan_epoch`` over the filled slots, which must be slots 0 .. len-1).  The plan is drawn and
-        its table uploaded before the first batch; ``plan`` of the most recent call is kept as ``last_plan``."""
+        its table uploaded before the first batch; ``plan`` of the most recent call is kept as ``last_plan``.  With
+        ``augment`` the plan is ``plan_epoch_augmented``'s (an ``AugmentedPlan``): its entries are uploaded beside the table,
+        and every batch it flags goes through the warp kernels, the others through the plain gather."""
         n = len(self)
         if n == 0 or not all(self._filled[:n]):
             raise RuntimeError("CubeCache.epoch: fill slots 0 .. len-1 first")
-        plan = plan_epoch(n, batch_size, (self.H, self.W), patch, shuffle, random_crop, flips, drop_last, generator)
+        if augment is None:
+            plan = plan_epoch(n, batch_size, (self.H, self.W), patch, shuffle, random_crop, flips, drop_last, generator)
+        else:
+            plan = plan_epoch_augmented(n, batch_size, (self.H, self.W), self.C, augment, patch, shuffle, random_crop, flips,
+                                        drop_last, generator)
         self.last_plan = plan
         return self._serve(plan)
 
-    def _serve(self, plan: EpochPlan) -> Iterator[dict]:
+    def _serve(self, plan) -> Iterator[dict]:
         if not plan.batches:
             return
         h, w = plan.window
         with torch.cuda.device(self.device):
             table = plan.table.pin_memory().to(self.device, non_blocking=True)     # once per epoch, asynchronous
+            warped = getattr(plan, "warped", None)
+            entries = plan.entries.pin_memory().to(self.device, non_blocking=True) if warped and any(warped) else None
         self._table = table             # (alive until the next epoch's table replaces it, also when this iterator is dropped early)
+        self._entries = entries
         order = plan.order.tolist()
         base = table.data_ptr()
-        for start, stop in plan.batches:
-            yield self._gather(base + 16 * start, order[start:stop], h, w)
+        for b, (start, stop) in enumerate(plan.batches):
+            if entries is not None and warped[b]:
+                yield self._warp(entries.data_ptr() + 64 * start, order[start:stop], h, w)
+            else:
+                yield self._gather(base + 16 * start, order[start:stop], h, w)
 
     def release(self, slot_tensor=None) -> None:
         """Mark an output buffer as consumed up to this point of the current stream.  Only needed when the next batch that

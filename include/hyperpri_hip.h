@@ -556,6 +556,28 @@ int hpri_cube_gather(const void* cache, int cache_dtype, int slots, int Hs, int 
 int hpri_mask_gather(const unsigned char* masks, int slots, int Hs, int Ws, const int* table, int N, int h, int w,
                      float* dst, hipStream_t stream);
 
+/* ---- cube cache, augmenting gather (cache_warp.hip; hyperpri_amd/cache.py: CubeAugment) -------------------
+ * The batch resampled from the cached slots through one affine map per sample (rotation, zoom, sub-pixel shift, flips), with a
+ * photometric gain / offset and a run of dropped bands; the mask follows through the same map, nearest neighbour.
+ * Warp entry: 64 bytes = 16 32-bit words per sample, in DEVICE memory, 16-byte aligned:
+ *     word 0 int32 slot | 1 int32 drop_lo | 2 int32 drop_n | 3 reserved (0) | 4..9 fp32 a00, a01, cx, a10, a11, cy |
+ *     10 fp32 gain | 11 fp32 offset | 12..15 reserved (0)
+ * Output pixel (y, x) of an h x w window:  u = x - (w-1)/2, v = y - (h-1)/2 (exact in fp32),
+ *     sx = a00*u + a01*v + cx,  sy = a10*u + a11*v + cy       (source column / row, pixel centres at integers, fp32)
+ *   hpri_cube_warp  dst[n, y, x, c] = gain * bilinear(slot, sy, sx, c) + offset for c < C: neighbours (floor sy, floor sx), (+0,+1),
+ *                   (+1,+0), (+1,+1) with weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy*fx in fp32 (f16 slots convert on load); a
+ *                   neighbour outside [0,Hs) x [0,Ws) counts as 0 and is not loaded, nor is one of weight 0 (integer sx, sy with
+ *                   gain 1 and offset 0 return the stored bits).  Channels [drop_lo, drop_lo + drop_n) are exactly 0 after gain and
+ *                   offset; pad channels [C, cs) are exactly 0 whatever the offset.  dst: (N, h, w, cs) fp32.
+ *   hpri_mask_warp  dst[n, 0, y, x] = (float)mask[slot, floor(sy + 0.5), floor(sx + 0.5)], 0 outside the frame; the same entries.
+ * The window may be larger than the frame (zero fill); h, w <= 4096.  The launchers cannot read the entries: the kernels clamp the
+ * slot into the cache, sx / sy in floating point into [-1, Ws] / [-1, Hs] (a NaN too) and the drop run into [0, cs], so a bad
+ * entry yields a wrong picture but never an access outside the buffers. */
+int hpri_cube_warp(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, int C, const int* entries, int N,
+                   int h, int w, float* dst, hipStream_t stream);
+int hpri_mask_warp(const unsigned char* masks, int slots, int Hs, int Ws, const int* entries, int N, int h, int w, float* dst,
+                   hipStream_t stream);
+
 /* ---- colour-coded segmentation maps (segmap.hip; hyperpri_amd/evaluate.py) --------------------------------
  * The per-pixel arithmetic of eval_color_segmaps (PLTrainer.py:219-267) minus matplotlib: three bands of the image as a
  * gamma-corrected pseudo-RGB picture (:236-240, `img[hsi_rgb] ** (1 / 2.2)`), prediction and ground truth painted in the
