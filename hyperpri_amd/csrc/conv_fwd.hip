@@ -720,6 +720,8 @@ static int conv_fwd_bf16_impl(const float* x, int x_cs, int x_coff, const void* 
   a.H2 = H2; a.W2 = W2; a.py0 = py0; a.px0 = px0; a.Cup = Cup;
   a.plp = reinterpret_cast<h16_t*>(planes); a.pl_cs = pl_cs; a.pl_coff = pl_coff;
   if (epi == HPRI_E_DIRECT) HPRI_REQUIRE(a.y_cw + y_coff <= y_cs, "conv_fwd_bf16: output channels exceed the channel stride");
+  // the grid covers Cout_pad channels: a wider y_cw would stay unwritten (and the split-K finish would read past its slab rows)
+  if (epi == HPRI_E_DIRECT) HPRI_REQUIRE(a.y_cw <= Cout_pad, "conv_fwd_bf16: y_cw exceeds Cout_pad");
   if (amode == HPRI_A_S2D || epi == HPRI_E_D2S) {
     HPRI_REQUIRE(KS == 1, "conv_fwd_bf16: S2D/D2S need KS == 1");
     HPRI_REQUIRE(Cup > 0 && Cup % 4 == 0, "conv_fwd_bf16: Cup must be a positive multiple of 4");
@@ -794,6 +796,8 @@ extern "C" int hpri_conv_fwd(const float* x, int x_cs, int x_coff, const float* 
   a.y_cw = y_cw < Cout ? Cout : y_cw; a.accumulate = accumulate & 1; a.relu = (accumulate >> 1) & 1;
   a.H2 = H2; a.W2 = W2; a.py0 = py0; a.px0 = px0; a.Cup = Cup;
   a.plp = nullptr; a.pl_cs = 0; a.pl_coff = 0;
+  // the grid covers Cout_pad channels: a wider y_cw would stay unwritten (and the split-K finish would read past its slab rows)
+  if (epi == HPRI_E_DIRECT) HPRI_REQUIRE(a.y_cw <= Cout_pad, "conv_fwd: y_cw exceeds Cout_pad");
   a.ksplit = conv_ksplit(N, H, W, Cin_pad, Cout_pad, KS, epi, amode);
   a.ws = ws;
   if (a.ksplit > 1) {

@@ -121,7 +121,8 @@ int hpri_fingerprint(const void* w, long long n_words, unsigned long long* out, 
  * Replaces F.conv2d / F.conv3d / F.linear / F.conv_transpose2d forward and their data gradients
  * (model_parts.py:22,25,63,96; models.py:108,169,177,198).  hpri_conv_fwd_plan (host only) returns the split-K
  * factor chosen for the shape, the workspace it needs, and the number of BatchNorm partial records: stats
- * (optional) receives stat_tiles * Cout_pad float4 (mean, M2, count, 0), image-major. */
+ * (optional) receives stat_tiles * Cout_pad float4 (mean, M2, count, 0), image-major.  y_cw (Cout <= y_cw <= Cout_pad) channels of
+ * the output view are written, [Cout, y_cw) as zeros; `accumulate` bit 1: ReLU of result + bias, bit 0: y += that, in this order. */
 int hpri_conv_fwd_plan(int N, int H, int W, int Cin_pad, int Cout_pad, int KS, int amode, int epi, int* ksplit,
                        int* stat_tiles, size_t* ws_floats);
 int hpri_conv_fwd(const float* x, int x_cs, int x_coff, const float* wp, const float* bias, float* y, int y_cs,
