@@ -5,10 +5,11 @@ Drop-in ``torch.nn.Module`` replacements for the reference's ``src/Experiments/m
 """
 from .cache import CubeAugment, CubeCache, plan_epoch, plan_epoch_augmented  # noqa: F401
 from .evaluate import (SplitPrediction, color_classmaps, color_segmaps, default_class_palette, evaluate_multiclass,  # noqa: F401
-                       predict_split, test_net, validate_net, write_segmaps)
+                       predict_split, test_net, tta_merge, validate_net, write_segmaps, write_spreadmaps)
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)
+from .tta import TTA, VIEW_NAMES, apply_view, invert_view, tta_merge_reference  # noqa: F401
 from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss, FocalLoss, forward_loss, FusedAdam, FusedSGD,  # noqa: F401
                       PRCurve, SegConfusion, SegCounts, SegLoss, SegmentationModel, TverskyLoss, argmax_classes, average_precision,
                       load_checkpoint, multiclass_metrics_from_confusion, network_state_dict)

@@ -67,6 +67,11 @@ quantity's stream), entry j again for the j-th sample served:
   8. ``drop``: a run of bands is dropped when ``drop < probability``;
   9. ``run = min(1 + floor(r * max_run), max_run, C)``;   10. ``drop_lo = min(floor(r * (C - run + 1)), C - run)``.
 A batch in which no sample needs the warp (identity geometry, gain 1, offset 0, no drop) goes through the plain gather.
+
+Views for test-time augmentation (``view``, ``epoch_views``, ``view_warp_entries``; hyperpri_amd/tta.py) -- opt-in as well.  The
+eight dihedral views of a whole frame, bit for bit: the four that keep the axes through the plain gather's flip flags, the four
+that swap them through the warp kernels with a (W, H) window and entries of exact 0 / +-1 (``view_warp_entries`` says why every
+source coordinate is then an integer in fp32), written into the same output slots.
 """
 from __future__ import annotations
 
@@ -203,6 +208,35 @@ def warp_entries(slots, tops, lefts, flip_h, flip_w, window, angle, zoom, shift_
     e[:, 0] = np.asarray(slots, dtype=np.int64)
     e[:, 1] = np.asarray(drop_lo, dtype=np.int64)
     e[:, 2] = np.asarray(drop_n, dtype=np.int64)
+    e[:, 4:12] = f.astype(np.float32).view(np.int32)
+    return torch.from_numpy(e)
+
+
+# the matrices (a00, a01, a10, a11) of the four views that swap the axes (hyperpri_amd/tta.py): exact 0 / +-1
+_VIEW_MATRIX = {"rot90": (0.0, -1.0, 1.0, 0.0), "rot270": (0.0, 1.0, -1.0, 0.0), "transpose": (0.0, 1.0, 1.0, 0.0),
+                "antitranspose": (0.0, -1.0, -1.0, 0.0)}
+
+
+def view_warp_entries(slots, view: str, frame: Tuple[int, int]) -> torch.Tensor:
+    """The (n, 16) int32 warp entries with which ``CubeCache.view`` makes ``view`` -- ``rot90``, ``rot270``, ``transpose`` or
+    ``antitranspose`` -- of whole ``frame`` = (H, W) cubes: the output window is (W, H), the matrix holds exact 0 / +-1, the centre
+    is the frame's, ``((W - 1) / 2, (H - 1) / 2)``, gain 1, offset 0, nothing dropped (a pure host function).
+
+    Every source coordinate is an integer in fp32, for even and odd H, W alike.  The kernels form ``u = x - (H - 1) / 2`` and
+    ``v = y - (W - 1) / 2`` for output pixel (y, x) of the (W, H) window, ``sx = fma(a00, u, fma(a01, v, cx))`` and
+    ``sy = fma(a10, u, fma(a11, v, cy))``.  With a00 = a11 = 0 these are ``sx = +-v + (W - 1) / 2`` and ``sy = +-u + (H - 1) / 2``
+    (the product with 0 adds a signed zero).  ``v`` and ``cx`` are both integers (odd W) or both half-integers (even W), and so
+    are ``u`` and ``cy`` with H: each sum or difference is an integer below 2^12, exact in fp32.  The bilinear weights are then 1
+    for one neighbour and 0 for the other three, which are not loaded: the stored bits come out."""
+    if view not in _VIEW_MATRIX:
+        raise ValueError(f"view_warp_entries: {view!r} does not swap the axes (the plain gather makes it)")
+    H, W = frame
+    n = len(slots)
+    a00, a01, a10, a11 = _VIEW_MATRIX[view]
+    f = np.empty((n, 8), dtype=np.float64)
+    f[:] = (a00, a01, (W - 1) / 2, a10, a11, (H - 1) / 2, 1.0, 0.0)
+    e = np.zeros((n, 16), dtype=np.int32)
+    e[:, 0] = np.asarray(slots, dtype=np.int64)
     e[:, 4:12] = f.astype(np.float32).view(np.int32)
     return torch.from_numpy(e)
 
@@ -513,6 +547,83 @@ class CubeCache:
                 yield self._warp(entries.data_ptr() + 64 * start, order[start:stop], h, w)
             else:
                 yield self._gather(base + 16 * start, order[start:stop], h, w)
+
+    # ---- views for test-time augmentation (hyperpri_amd/tta.py) -----------------------------------------------------
+    def _warp_transposed(self, entries_ptr: int, slots: Sequence[int]) -> dict:
+        """``_warp`` for a (W, H) window of whole frames.  The window has as many pixels as the frame, so it is written into
+        the (H, W) output buffers themselves, read as (n, W, H, cs): ``_take_slot`` sees the frame's shape, and alternating
+        between the two orientations allocates nothing.  Slot rotation and stream ordering are ``_warp``'s."""
+        n = len(slots)
+        H, W = self.H, self.W
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            k = self._take_slot(n, H, W, cur)
+            s = ctypes.c_void_p(cur.cuda_stream)
+            ep = ctypes.c_void_p(entries_ptr)
+            _lib.call("hpri_cube_warp", _p(self._cubes), _DT[self.store_dtype], self.capacity, H, W, self.cs, self.C, ep,
+                      n, W, H, _p(self._out[k]), s)
+            _lib.call("hpri_mask_warp", _p(self._masks), self.capacity, H, W, ep, n, W, H, _p(self._mout[k]), s)
+        x = self._out[k][:n].view(n, W, H, self.cs)[:, :, :, :self.C].permute(0, 3, 1, 2)       # logical (N,C,W,H), channels-last strides
+        if self.unsqueeze:
+            x = x.unsqueeze(1)
+        x._hpri_zero_padded = True
+        x._hpri_slot = k
+        return {'image': x, 'mask': self._mout[k][:n].view(n, 1, W, H), 'index': [self._names[i] for i in slots]}
+
+    def view(self, indices: Sequence[int], view: str) -> dict:
+        """``{'image', 'mask', 'index'}`` of the WHOLE frame of the cached cubes ``indices`` in one of the eight dihedral views of
+        ``hyperpri_amd.tta`` -- image and mask alike, bit for bit ``apply_view`` of ``batch(indices)``.  ``id``, ``flip_h``,
+        ``flip_w`` and ``rot180`` are the plain gather with the table's flip flags; ``rot90``, ``rot270``, ``transpose`` and
+        ``antitranspose`` come out as (W, H) frames from the warp kernels with the entries of ``view_warp_entries`` (exact
+        0 / +-1, every source coordinate an integer in fp32: see there).  Uploads 16 or 64 bytes per sample; the output slots
+        rotate, and the streams are ordered, as for ``batch()``."""
+        from .tta import view_code
+        code = view_code(view)
+        idx = [int(i) for i in indices]
+        if not idx:
+            raise ValueError("CubeCache.view: no indices")
+        self._check_filled(idx)
+        if code >= 4:
+            entries = view_warp_entries(idx, view, (self.H, self.W)).to(self.device)
+            out = self._warp_transposed(entries.data_ptr(), idx)
+            entries.record_stream(torch.cuda.current_stream(self.device))
+            return out
+        flags = {"id": 0, "flip_h": 1, "flip_w": 2, "rot180": 3}[view]
+        table = torch.tensor([[i, 0, 0, flags] for i in idx], dtype=torch.int32).to(self.device)
+        out = self._gather(table.data_ptr(), idx, self.H, self.W)
+        table.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def epoch_views(self, batch_size: int, views: Sequence[str]) -> Iterator[dict]:
+        """One unshuffled pass over the filled slots (which must be slots 0 .. len-1) for test-time augmentation: yields
+        ``{'mask', 'index', 'views', 'image_of'}`` -- ``mask`` and ``index`` of the identity orientation, ``views`` the names
+        asked for, and ``image_of(name)``, which gathers that view of the batch's images when it is called.
+
+        Every ``image_of`` call is a gather into the next output slot (the first ``image_of('id')`` of a batch hands out the
+        gather that made ``mask``): a view tensor -- and ``mask`` -- is valid until ``out_slots`` further gathers.  The consumer
+        must be done with one view (and have copied the mask) before it asks for the next; ``predict_split`` is."""
+        from .tta import view_code
+        names = [views] if isinstance(views, str) else list(views)
+        for v in names:
+            view_code(v)
+        if batch_size <= 0:
+            raise ValueError("CubeCache.epoch_views: batch_size must be positive")
+        n = len(self)
+        if n == 0 or not all(self._filled[:n]):
+            raise RuntimeError("CubeCache.epoch_views: fill slots 0 .. len-1 first")
+        return self._serve_views(n, batch_size, tuple(names))
+
+    def _serve_views(self, n: int, batch_size: int, names: Tuple[str, ...]) -> Iterator[dict]:
+        for start in range(0, n, batch_size):
+            slots = list(range(start, min(start + batch_size, n)))
+            first = self.view(slots, "id")
+            fresh = [first['image']]
+
+            def image_of(name: str, slots=slots, fresh=fresh) -> torch.Tensor:
+                image = fresh.pop() if fresh and name == "id" else self.view(slots, name)['image']
+                fresh.clear()
+                return image
+            yield {'mask': first['mask'], 'index': first['index'], 'views': names, 'image_of': image_of}
 
     def release(self, slot_tensor=None) -> None:
         """Mark an output buffer as consumed up to this point of the current stream.  Only needed when the next batch that

@@ -12,6 +12,14 @@ the cubes stay on the card; what crosses PCIe is a few scalars, the 501-point cu
     write_segmaps(fig_dir, pred, cache.epoch(batch_size=2, shuffle=False), val["best_threshold"])
     test  = test_net(predict_split(net, test_batches), val["best_threshold"])
 
+Test-time augmentation (``hyperpri_amd.tta``, ``csrc/tta.hip``) is opt-in and changes nothing when it is off: with ``tta=TTA()`` the
+network sees every view of a batch, ``CubeCache.epoch_views`` makes the views with the gathers that read the cube anyway, and one
+``hpri_tta_merge`` per batch brings the logits back to the frame and merges them:
+
+    tta  = TTA(views=("id", "flip_w", "flip_h", "rot180"), merge="prob", spread=True)
+    pred = predict_split(net, cache.epoch_views(2, tta.views), tta=tta)      # pred.logits: the logit of the mean probability
+    val  = validate_net(pred); write_spreadmaps(fig_dir, pred)
+
 Lightning-free and torchmetrics-free like ``trainer.py``, whose device pieces this module composes (``hpri_bce_logits_fwd``,
 ``SegCounts``, ``PRCurve``, ``best_dice_threshold``, ``average_precision``); the maps are one kernel of their own
 (``csrc/segmap.hip``).  There is no CPU fallback: tensors must be fp32 on a ROCm device.
@@ -28,6 +36,7 @@ from torch import nn
 
 from . import _lib
 from .engine import _p, _require_cuda, _stream
+from .tta import TTA, VIEW_CODES, apply_view, view_shape
 from .trainer import (MAX_CLASSES, PRCurve, SegCounts, _TARGET_KIND, _class_logits, _class_target, _confusion_pass, _ignore_args,
                       _split_counts, average_precision, best_dice_threshold, multiclass_metrics_from_confusion)
 
@@ -48,6 +57,7 @@ class SplitPrediction:
     offsets: List[int]              # len(names) + 1
     sizes: List[Tuple[int, int]]
     names: List[object]
+    spread: Optional[torch.Tensor] = None   # fp32, flat, the offsets of ``logits``: the views' disagreement (``TTA(spread=True)`` only)
 
     def __len__(self) -> int:
         return len(self.names)
@@ -76,14 +86,88 @@ def _names(index, n: int) -> List[object]:
     return names
 
 
-def predict_split(network: nn.Module, batches: Iterable[dict]) -> SplitPrediction:
+def tta_merge(view_logits: Sequence[torch.Tensor], views: Sequence[str], merge: str = "prob", spread: bool = False,
+              frame: Optional[Tuple[int, int]] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """One ``hpri_tta_merge`` launch (csrc/tta.hip; the contract is restated by ``tta.tta_merge_reference``): ``view_logits[v]`` is
+    the contiguous fp32 (N, K, hv, wv) device tensor a network gave for view ``views[v]``; returns ``(out, spread)``, ``out``
+    (N, K, h, w) in the original frame and ``spread`` (N, h, w) or None.  ``frame`` = (h, w) is checked against the views' shapes
+    when given.  Pointers and view codes travel as kernel arguments: nothing is uploaded, nothing synchronises."""
+    import ctypes
+    V = len(view_logits)
+    if not 1 <= V <= len(VIEW_CODES) or len(views) != V:
+        raise ValueError(f"tta_merge: need 1 to {len(VIEW_CODES)} views and one tensor per view, got {V} tensors for {len(views)} views")
+    if merge not in ("prob", "logit"):
+        raise ValueError(f"tta_merge: merge must be 'prob' or 'logit', got {merge!r}")
+    codes = [VIEW_CODES[v] if v in VIEW_CODES else None for v in views]
+    if None in codes:
+        raise ValueError(f"tta_merge: unknown view in {tuple(views)!r}")
+    first = view_logits[0]
+    for x in view_logits:
+        _require_cuda(x, "test-time augmentation logits")
+        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != first.device:
+            raise ValueError("tta_merge: every view must be a contiguous fp32 (N, K, hv, wv) tensor on one device")
+    N, K, hv, wv = (int(v) for v in first.shape)
+    h, w = (wv, hv) if codes[0] >= 4 else (hv, wv)
+    if frame is not None and (h, w) != tuple(frame):
+        raise ValueError(f"tta_merge: view {views[0]!r} of a {frame[0]}x{frame[1]} frame cannot be {hv}x{wv}")
+    for x, v in zip(view_logits, views):
+        if tuple(x.shape) != (N, K, *view_shape(v, h, w)):
+            raise ValueError(f"tta_merge: view {v!r} of a {h}x{w} frame must be {(N, K, *view_shape(v, h, w))}, got {tuple(x.shape)}")
+    if not 1 <= K <= MAX_CLASSES:
+        raise ValueError(f"tta_merge: the number of planes must lie in [1, {MAX_CLASSES}], got {K}")
+    with torch.cuda.device(first.device):
+        out = torch.empty((N, K, h, w), dtype=torch.float32, device=first.device)
+        sp = torch.empty((N, h, w), dtype=torch.float32, device=first.device) if spread else None
+        ptrs = (ctypes.c_void_p * V)(*[x.data_ptr() for x in view_logits])
+        cds = (ctypes.c_int * V)(*codes)
+        _lib.call("hpri_tta_merge", ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(cds, ctypes.c_void_p), V, N, K, h, w,
+                  1 if merge == "prob" else 0, _p(out), _p(sp), _stream())
+    return out, sp
+
+
+def _view_logits(network: nn.Module, batch: dict, tta: TTA, planes: int, frame: Tuple[int, int], who: str) -> List[torch.Tensor]:
+    """The network's fp32 logits for every view of ``tta``, each a contiguous (N, planes, hv, wv) tensor of its own.  A view's image
+    is ``batch['image_of'](view)`` when the batch has that key (``CubeCache.epoch_views``: the gather that reads the cube anyway
+    makes the view, and a view is finished with before the next one is asked for); otherwise ``apply_view(batch['image'],
+    view).contiguous()`` -- the torch fallback, which costs an ATen copy of the cube per view."""
+    h, w = frame
+    outs: List[torch.Tensor] = []
+    for v in tta.views:
+        image = batch["image_of"](v) if "image_of" in batch else apply_view(batch["image"], v).contiguous()
+        _require_cuda(image, "evaluation image")
+        pred = network(image)
+        if isinstance(pred, tuple):                      # analyze=True networks return (pred, features)
+            pred = pred[0]
+        n = int(pred.shape[0])
+        hv, wv = view_shape(v, h, w)
+        if pred.numel() != n * planes * hv * wv or (int(pred.shape[-2]), int(pred.shape[-1])) != (hv, wv):
+            raise ValueError(f"{who}: view {v!r} of a {h}x{w} frame needs ({n}, {planes}, {hv}, {wv}) logits, got {tuple(pred.shape)}")
+        x = pred.detach().to(torch.float32).reshape(n, planes, hv, wv).contiguous()
+        if x.data_ptr() == pred.data_ptr():              # a copy: the network may hand out a buffer that its next forward rewrites
+            x = x.clone()
+        outs.append(x)
+    return outs
+
+
+def predict_split(network: nn.Module, batches: Iterable[dict], tta: Optional[TTA] = None) -> SplitPrediction:
     """``pl_trainer.predict(pl_model, loader)`` (PLTrainer.py:530-532, 626-629) without the host: the network runs in ``eval()``
     under ``torch.inference_mode()`` over ``batches`` -- any iterable of ``{'image', 'mask', 'index'}`` dicts with device tensors,
     ``CubeCache.epoch(batch_size, shuffle=False)`` or a DataLoader whose batches were moved to the card -- and every batch's
     logits and mask are kept on the device, where ``predict_step`` does ``.cpu()``.  ``(pred, features)`` of ``analyze=True``
     networks is unwrapped; a ragged last batch and images of different sizes are fine.  The previous train / eval mode of the
-    network is restored afterwards."""
+    network is restored afterwards.
+
+    ``tta`` (``hyperpri_amd.TTA``; None: nothing below happens): test-time augmentation.  Per batch the mask is copied and the names
+    are recorded first; the network then runs once per view (``_view_logits``: the views come from ``batch['image_of']`` --
+    ``CubeCache.epoch_views(batch_size, tta.views)`` -- or, for batches with a plain ``'image'``, from ``apply_view``, an ATen copy
+    of the cube per view); one ``hpri_tta_merge`` brings the views' logits back to the frame and merges them, and the result is
+    stored as above.  With ``merge="prob"`` what is stored is the logit of the mean probability: ``logits`` stays a store of
+    logits, and ``validate_net``, ``test_net`` and ``write_segmaps`` work on it unchanged.  ``tta.spread`` fills
+    ``SplitPrediction.spread``."""
+    if tta is not None and not isinstance(tta, TTA):
+        raise TypeError(f"predict_split: tta must be a hyperpri_amd.TTA or None, got {type(tta).__name__}")
     was_training = network.training
+    spreads: List[torch.Tensor] = []
     logits: List[torch.Tensor] = []
     masks: List[torch.Tensor] = []
     offsets, sizes, names = [0], [], []
@@ -91,6 +175,27 @@ def predict_split(network: nn.Module, batches: Iterable[dict]) -> SplitPredictio
     try:
         with torch.inference_mode():
             for batch in batches:
+                if tta is not None:
+                    mask = batch["mask"]
+                    _require_device(mask, "evaluation mask")
+                    if mask.dim() < 2:
+                        raise ValueError(f"evaluate: need a (N, 1, h, w) or (N, h, w) mask, got {tuple(mask.shape)}")
+                    h, w = int(mask.shape[-2]), int(mask.shape[-1])
+                    # first of all: the views below rotate through the output slots the mask lives in
+                    masks.append(mask.to(torch.float32).reshape(-1).clone())
+                    n = mask.numel() // (h * w)
+                    names.extend(_names(batch.get("index"), n))
+                    views = _view_logits(network, batch, tta, 1, (h, w), "predict_split")
+                    if int(views[0].shape[0]) != n:
+                        raise ValueError(f"evaluate: {int(views[0].shape[0])} images of logits for {n} masks")
+                    merged, sp = tta_merge(views, tta.views, tta.merge, tta.spread, (h, w))
+                    logits.append(merged.reshape(-1))
+                    if sp is not None:
+                        spreads.append(sp.reshape(-1))
+                    for _ in range(n):
+                        offsets.append(offsets[-1] + h * w)
+                        sizes.append((h, w))
+                    continue
                 image, mask = batch["image"], batch["mask"]
                 _require_cuda(image, "evaluation image")
                 _require_device(mask, "evaluation mask")
@@ -111,7 +216,7 @@ def predict_split(network: nn.Module, batches: Iterable[dict]) -> SplitPredictio
                     sizes.append((h, w))
             if not logits:
                 raise ValueError("predict_split: no batches")
-            return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names)
+            return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, torch.cat(spreads) if spreads else None)
     finally:
         network.train(was_training)
 
@@ -284,6 +389,22 @@ def write_segmaps(directory: str, split_pred: SplitPrediction, batches: Iterable
     return paths
 
 
+def write_spreadmaps(directory: str, split_pred: SplitPrediction) -> List[str]:
+    """The disagreement maps of a ``predict_split(tta=TTA(spread=True))``: per image the standard deviation over the views of the
+    foreground probability as 8-bit grey, ``(uint8)(255 * min(1, 2 * std) + 0.5)`` (a standard deviation cannot exceed 1/2).
+    Writes ``<name>_spread.png`` with PIL when PIL is importable, ``<name>_spread.npy`` (uint8 (h, w)) otherwise; returns the
+    paths.  One byte per pixel goes to the host."""
+    if split_pred.spread is None:
+        raise ValueError("write_spreadmaps: the prediction holds no spread (predict_split(..., tta=TTA(spread=True)))")
+    os.makedirs(directory, exist_ok=True)
+    grey = (torch.clamp(split_pred.spread * 2.0, 0.0, 1.0) * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
+    paths: List[str] = []
+    for i, name in enumerate(split_pred.names):
+        a, b, (h, w) = split_pred.offsets[i], split_pred.offsets[i + 1], split_pred.sizes[i]
+        paths.append(_write_picture(os.path.join(directory, f"{name}_spread"), grey[a:b].reshape(h, w)))
+    return paths
+
+
 # ---------------------------------------------------------------------------------------------------
 # The multi-class counterparts (csrc/multiclass.hip, hpri_segmap_classes): one pass over a split, nothing stored
 # ---------------------------------------------------------------------------------------------------
@@ -353,7 +474,8 @@ def color_classmaps(image: torch.Tensor, classes: torch.Tensor, palette: Optiona
 def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes: int, ignore_index: Optional[int] = None,
                         class_weight: Optional[torch.Tensor] = None, segmap_dir: Optional[str] = None,
                         palette: Optional[Sequence[Sequence[float]]] = None, alpha: float = ALPHA,
-                        bands: Optional[Sequence[int]] = None, gamma: Optional[float] = None) -> Dict[str, object]:
+                        bands: Optional[Sequence[int]] = None, gamma: Optional[float] = None,
+                        tta: Optional[TTA] = None) -> Dict[str, object]:
     """A split under a multi-class network in ONE pass, with ``predict_split``'s contract (``eval()`` under
     ``torch.inference_mode()``, the previous mode restored, ``{'image', 'mask', 'index'}`` batches with device tensors, ragged
     batches and images of different sizes fine) -- but the (N, K, h, w) logits are never stored.  Per batch, on the device:
@@ -367,7 +489,15 @@ def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes
 
     One host synchronisation at the end.  Returns ``ce_loss`` (what ``nn.CrossEntropyLoss(class_weight, ignore_index)`` gives over
     all pixels of the split), the entries of ``multiclass_metrics_from_confusion``, ``names`` and, with ``segmap_dir``, ``paths``.
-    Raises ``ValueError`` if a mask held a value outside [0, num_classes) that was not ``ignore_index``."""
+    Raises ``ValueError`` if a mask held a value outside [0, num_classes) that was not ``ignore_index``.
+
+    ``tta`` (``hyperpri_amd.TTA``; None: nothing below happens): the network runs once per view (``_view_logits``, as in
+    ``predict_split``) and one ``hpri_tta_merge`` per batch replaces the logits by the merged ones before the confusion and the
+    cross-entropy pass -- with ``merge="prob"`` the log of the mean softmax, whose softmax is that mean: argmax and cross-entropy
+    need no change.  With ``tta.spread`` and ``segmap_dir`` the fraction of views that disagree with the merged class is also
+    written per image, as ``<name>_spread.npy`` (fp32 (h, w)); ``spread_paths`` lists the files."""
+    if tta is not None and not isinstance(tta, TTA):
+        raise TypeError(f"evaluate_multiclass: tta must be a hyperpri_amd.TTA or None, got {type(tta).__name__}")
     K = int(num_classes)
     if not 2 <= K <= MAX_CLASSES:
         raise ValueError(f"evaluate_multiclass: the number of classes must lie in [2, {MAX_CLASSES}], got {num_classes}")
@@ -378,18 +508,31 @@ def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes
     was_training = network.training
     names: List[object] = []
     paths: List[str] = []
+    spread_paths: List[str] = []
     counts = totals = weight = None
     use_ignore, ignore = _ignore_args(ignore_index)
     network.eval()
     try:
         with torch.inference_mode():
             for batch in batches:
-                image, mask = batch["image"], batch["mask"]
-                _require_cuda(image, "evaluation image")
-                _require_device(mask, "evaluation mask")
-                pred = network(image)
-                if isinstance(pred, tuple):                  # analyze=True networks return (pred, features)
-                    pred = pred[0]
+                spread = None
+                if tta is not None:
+                    mask = batch["mask"]
+                    _require_device(mask, "evaluation mask")
+                    if mask.dim() < 2:
+                        raise ValueError(f"evaluate_multiclass: need a (N, 1, h, w) or (N, h, w) mask, got {tuple(mask.shape)}")
+                    mask = mask.clone()                      # first of all: the views rotate through the output slots it lives in
+                    views = _view_logits(network, batch, tta, K, (int(mask.shape[-2]), int(mask.shape[-1])), "evaluate_multiclass")
+                    pred, spread = tta_merge(views, tta.views, tta.merge, tta.spread and segmap_dir is not None)
+                    if segmap_dir is not None:               # the picture shows the identity orientation
+                        image = batch["image_of"]("id") if "image_of" in batch else batch["image"]
+                else:
+                    image, mask = batch["image"], batch["mask"]
+                    _require_cuda(image, "evaluation image")
+                    _require_device(mask, "evaluation mask")
+                    pred = network(image)
+                    if isinstance(pred, tuple):                  # analyze=True networks return (pred, features)
+                        pred = pred[0]
                 if pred.dim() != 4 or int(pred.shape[1]) != K:
                     raise ValueError(f"evaluate_multiclass: need (N, {K}, h, w) logits, got {tuple(pred.shape)}")
                 x = _class_logits(pred.detach().to(torch.float32), "evaluation logits")
@@ -416,6 +559,11 @@ def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes
                     rgb = color_classmaps(image, classes, palette=palette, alpha=alpha, bands=bands, gamma=gamma).cpu().numpy()
                     for j in range(n):
                         paths.append(_write_picture(os.path.join(segmap_dir, f"{batch_names[j]}_seg"), rgb[j]))
+                    if spread is not None:
+                        maps = spread.cpu().numpy()
+                        for j in range(n):
+                            spread_paths.append(os.path.join(segmap_dir, f"{batch_names[j]}_spread.npy"))
+                            np.save(spread_paths[-1], maps[j])
                 names.extend(batch_names)
             if counts is None:
                 raise ValueError("evaluate_multiclass: no batches")
@@ -428,4 +576,6 @@ def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes
     out["names"] = names
     if segmap_dir is not None:
         out["paths"] = paths
+        if tta is not None and tta.spread:
+            out["spread_paths"] = spread_paths
     return out

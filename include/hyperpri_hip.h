@@ -686,6 +686,30 @@ int hpri_seg_loss_bwd(const float* logits, const float* target, int n_img, long 
                       float focal_gamma, float focal_alpha, float w_overlap, int per_image, const double* state,
                       size_t state_doubles, const float* grad_out, float* dlogits, hipStream_t stream);
 
+/* ---- test-time augmentation, the merge (tta.hip; hyperpri_amd/tta.py, evaluate.py) --------------------------
+ * The logits of V dihedral views of a batch, brought back to the original h x w frame and merged in one launch.
+ *   views   HOST array of V device pointers (1 <= V <= 8); view v is a contiguous fp32 (N, K, hv, wv) tensor, (hv, wv) = (h, w)
+ *           for codes 0 .. 3 and (w, h) for codes 4 .. 7.  Pointers and codes travel as kernel arguments: nothing is uploaded.
+ *   codes   HOST array of V view codes: 0 id, 1 flip_h (rows reversed), 2 flip_w (columns reversed), 3 rot180, 4 rot90
+ *           (torch.rot90(x, 1, (-2, -1))), 5 rot270, 6 transpose, 7 antitranspose
+ *   N, K, h, w   images, planes (1 <= K <= 64) and the ORIGINAL frame;  mode  0 logit, 1 prob
+ *   out     (N, K, h, w) fp32;  spread  (N, h, w) fp32 or NULL (not computed)
+ * With s_v = view v's value at the pixel that (y, x) was sent to:
+ *   mode 0          out = (((s_0 + s_1) + s_2) ... + s_{V-1}) * (1 / V): fp32 adds in view order, one multiply by the fp32 quotient
+ *                   1 / V, nothing fused -- bit-reproducible, and the input bits for V = 1 with id.
+ *   mode 1, K = 1   p_v = 1 / (1 + exp(-s_v)), q_v = 1 / (1 + exp(s_v)) (each on its own: both tails stay accurate), means in view
+ *                   order;  out = log(max(mean p, FLT_MIN)) - log(max(mean q, FLT_MIN)), the logit of the mean probability.
+ *   mode 1, K > 1   per view the softmax over the K planes (row maximum subtracted), p_vk = exp(s_vk - m_v) * (1 / sum_v), the mean
+ *                   over the views, out_k = log(max(mean p_k, FLT_MIN)): log-probabilities, softmax(out) = mean p.
+ *   spread, K = 1   the population standard deviation over the views of p_v (both modes), two passes over registers
+ *   spread, K > 1   the fraction of views whose own argmax differs from the argmax of the merged out (lowest index among equal
+ *                   maxima, a NaN counts as the maximum)
+ * The logarithms are evaluated in fp64 and rounded once (an fp32 logarithm's error grows with the logit); exp, the divisions and
+ * the means are fp32.  NaN inputs propagate.  Every output element is written once and never read; no atomics; 64-bit offsets.  Argument errors (a null
+ * pointer, V, K, a code or mode out of range, a size <= 0) are reported before any launch. */
+int hpri_tta_merge(const float* const* views, const int* codes, int V, int N, int K, int h, int w, int mode, float* out,
+                   float* spread, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
