@@ -1586,7 +1586,10 @@ extern "C" int hpri_synth_fill(float* dst, long long n, unsigned long long seed,
 // nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True), model_parts.py:57 / models.py:195.
 // ATen semantics: src = dst * (in-1)/(out-1); i0 = (int)src; l1 = src - i0; i1 = i0 + (i0 < in-1).
 // The result is written at pixel offset (py0, px0) of a (possibly larger, padded) destination image.
+// No contraction: l1 must be the ROUNDED src minus its integer part, identically in the forward and the backward kernel (an fma
+// here would give the two different weights, and an l1 just below zero where src rounds up to an integer).
 __device__ __forceinline__ void bil_coord(int o, int in, int out, int* i0, int* i1, float* l0, float* l1) {
+#pragma clang fp contract(off)
   const float scale = (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f;
   const float src = scale * (float)o;
   const int a = (int)src;
@@ -1621,8 +1624,9 @@ __global__ void upsample2x_fwd_kernel(const float* __restrict__ x, int x_cs, int
   }
 }
 
-// gradient w.r.t. the low-res input as a GATHER (deterministic): input pixel (iy,ix) collects from the <= 4x4
-// output pixels whose interpolation footprint contains it.
+// gradient w.r.t. the low-res input as a GATHER (deterministic): input pixel (iy,ix) collects from the <= 5x5
+// output pixels whose interpolation footprint contains it (src moves by less than 1/2 per output and the footprint is the open
+// interval (i - 1, i + 1); the scan below covers 7 outputs per axis).
 __global__ void upsample2x_bwd_kernel(const float* __restrict__ dy, int dy_cs, int dy_coff, float* __restrict__ dx,
                                       int dx_cs, int dx_coff, int N, int H, int W, int H2, int W2, int py0, int px0,
                                       int C4, int accumulate) {

@@ -19,7 +19,9 @@ equal hpri_maxpool2_bwd + add within the roundings of that inversion: a misroute
 Largest ratio error / bound seen on MI355X: dbeta 0.056, dgamma 0.053, dx 0.34, recovered gradient 0.32; sums against the replaced
 route 0.044; engine routes: error with the routes on / (2 x error with them off + floor) at most 0.55 (the two errors are equal).
 
-Pooling forward: y and the pooled map of the one-pass kernel BIT FOR BIT those of hpri_bn_apply_relu_pl + hpri_maxpool2_fwd."""
+Pooling forward: y and the pooled map of the one-pass kernel BIT FOR BIT those of hpri_bn_apply_relu_pl + hpri_maxpool2_fwd
+(hpri_maxpool2_fwd itself is pinned against F.max_pool2d in test_gpu_glue_kernels.py, hpri_bn_apply_relu_pl in
+test_gpu_bn_kernels.py)."""
 import ctypes
 import os
 from collections import OrderedDict

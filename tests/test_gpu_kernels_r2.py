@@ -354,7 +354,8 @@ def test_copy_slice_any_rows_and_elements(lib, case, acc):
 def test_maxpool_over_bf16_rows(lib, shape):
     """hpri_maxpool2_fwd_x16 / hpri_maxpool2_bwd_x16 (round 4; model_parts.py:40 on a planes-only skip): forward == the fp32 kernel on the
     same (bf16-exact) values, fp32 output optional; backward == the fp32 kernel on those values, the gradient written / accumulated as
-    fp32 or as bf16 rows (rounded once per write)."""
+    fp32 or as bf16 rows (rounded once per write).  The fp32 forward it is compared with, hpri_maxpool2_fwd_pl, is pinned against
+    F.max_pool2d in test_gpu_glue_kernels.py; the fp32 backward in test_maxpool_backward_one_thread_per_window above."""
     N, H, W, C = shape
     torch.manual_seed(6)
     xs = C + 32                                               # the skip half of a wider plane buffer
