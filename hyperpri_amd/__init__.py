@@ -3,7 +3,8 @@
 Drop-in ``torch.nn.Module`` replacements for the reference's ``src/Experiments/models.py`` and
 ``model_parts.py`` whose forward/backward run in hand-written HIP kernels.  See DESIGN.md.
 """
-from .cache import CubeAugment, CubeCache, plan_epoch, plan_epoch_augmented  # noqa: F401
+from .cache import (CubeAugment, CubeCache, CubeDeform, deform_entries, elastic_lattice, plan_epoch, plan_epoch_augmented,  # noqa: F401
+                    plan_epoch_deformed)
 from .evaluate import (SplitPrediction, color_classmaps, color_segmaps, default_class_palette, evaluate_multiclass,  # noqa: F401
                        predict_split, test_net, tta_merge, validate_net, write_segmaps, write_spreadmaps)
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401

@@ -68,6 +68,31 @@ quantity's stream), entry j again for the j-th sample served:
   9. ``run = min(1 + floor(r * max_run), max_run, C)``;   10. ``drop_lo = min(floor(r * (C - run + 1)), C - run)``.
 A batch in which no sample needs the warp (identity geometry, gain 1, offset 0, no drop) goes through the plain gather.
 
+Deformation (``CubeDeform``, ``plan_epoch_deformed``, csrc/cache_deform.hip) -- opt-in again; without it nothing above changes.
+Elastic deformation, additive Gaussian noise and CutMix in the same pass.  Beside the warp entry a second 64-byte record per sample:
+    ``[mix_from, ry0, ry1, rx0, rx1, nodes_off, gy, gx, inv_pitch, noise_sigma, k0, k1, 0, 0, 0, 0]``  (words 8, 9 hold fp32 bits)
+  * elastic: a coarse lattice of random displacements (``(gy, gx, 2)`` fp32 = (dx, dy) in output pixels, nodes ``pitch`` pixels apart,
+    ``elastic_lattice``), interpolated by the uniform cubic B-spline into a per-pixel field that is added to the output coordinate
+    before the affine map -- the U-Net paper's form.  Cube and mask read the same field;
+  * noise: ``out = sigma * z + base`` with z from Philox4x32-10 under the sample's key ``(k0, k1)`` at the counter
+    ``(y * w + x) * (cs / 4) + c / 4`` (one call per channel quad) through Box-Muller.  Dropped and pad channels stay 0, the mask is
+    not touched;
+  * CutMix: the pixels of the rectangle ``[ry0, ry1) x [rx0, rx1)`` of sample s come from batch sample ``mix_from`` -- its slot, warp
+    entry and elastic field, image and mask alike (hard labels) --, the noise stays s's own.
+Draw order of ``plan_epoch_deformed``: first ``plan_epoch_augmented``'s draws, unchanged; then, ALL of them whatever the settings
+are, seven vectors ``torch.rand(n, dtype=torch.float64, generator=g)``:
+  1. ``elastic``: the sample is deformed when ``elastic < probability``;
+  2. ``noise_sigma = lo + r * (hi - lo)``;
+  3. ``cut``: the sample receives a rectangle when ``cut < probability``;
+  4. ``cut_h``: ``rh = clamp(round((min + r * (max - min)) * h), 1, h)``;   5. ``cut_w`` likewise with w;
+  6. ``cut_y``: ``ry0 = min(floor(r * (h - rh + 1)), h - rh)``;             7. ``cut_x`` likewise;
+  8. ``torch.randint(0, 2**32, (n, 2), dtype=torch.int64, generator=g)``: the noise keys;
+  9. last, and only when the elastic probability and sigma are both above 0:
+     ``torch.randn(n, gy, gx, 2, dtype=torch.float64, generator=g) * sigma``, rounded once to fp32 (last, so that its size shifts
+     no other quantity's stream).
+The CutMix partner of the j-th sample of a batch is the sample before it in that batch, cyclically (no draw); a batch of one has no
+CutMix.  A batch in which no sample needs any of the three goes through the warp pair or the plain gather as before.
+
 Views for test-time augmentation (``view``, ``epoch_views``, ``view_warp_entries``; hyperpri_amd/tta.py) -- opt-in as well.  The
 eight dihedral views of a whole frame, bit for bit: the four that keep the axes through the plain gather's flip flags, the four
 that swap them through the warp kernels with a (W, H) window and entries of exact 0 / +-1 (``view_warp_entries`` says why every
@@ -281,6 +306,116 @@ def plan_epoch_augmented(n: int, batch_size: int, frame: Tuple[int, int], channe
     return AugmentedPlan(plan.order, plan.table, entries, plan.batches, plan.window, warped)
 
 
+def _finite(v, what: str, n: int) -> Tuple[float, ...]:
+    try:
+        t = tuple(float(e) for e in v)
+    except TypeError:
+        t = ()
+    if len(t) != n or not all(math.isfinite(e) for e in t):
+        raise ValueError(f"CubeDeform: {what} must be {n} finite numbers, got {v!r}")
+    return t
+
+
+@dataclass(frozen=True)
+class CubeDeform:
+    """What ``plan_epoch_deformed`` draws per sample beyond ``CubeAugment`` (module docstring); the defaults are neutral.
+    Needs no device."""
+    elastic: Tuple[float, float, float] = (0.0, 0.0, 32.0)    # (probability, sigma of the node displacements in pixels, node pitch in pixels)
+    noise: Tuple[float, float] = (0.0, 0.0)                   # (lo, hi): the per-sample sigma is uniform in this range
+    cutmix: Tuple[float, float, float] = (0.0, 0.1, 0.5)      # (probability, smallest, largest side as a fraction of h and w)
+
+    def __post_init__(self):
+        p, sigma, pitch = _finite(self.elastic, "elastic = (probability, sigma, pitch)", 3)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"CubeDeform: the elastic probability must lie in [0, 1], got {p!r}")
+        if sigma < 0 or pitch < 4:
+            raise ValueError(f"CubeDeform: elastic needs sigma >= 0 and pitch >= 4, got {self.elastic!r}")
+        lo, hi = _finite(self.noise, "noise = (lo, hi)", 2)
+        if lo < 0 or lo > hi:
+            raise ValueError(f"CubeDeform: noise must be a range 0 <= lo <= hi, got {self.noise!r}")
+        cp, fmin, fmax = _finite(self.cutmix, "cutmix = (probability, min_frac, max_frac)", 3)
+        if not 0.0 <= cp <= 1.0:
+            raise ValueError(f"CubeDeform: the cutmix probability must lie in [0, 1], got {cp!r}")
+        if not 0.0 < fmin <= fmax <= 1.0:
+            raise ValueError(f"CubeDeform: cutmix needs 0 < min_frac <= max_frac <= 1, got {self.cutmix!r}")
+        object.__setattr__(self, "elastic", (p, sigma, pitch))
+        object.__setattr__(self, "noise", (lo, hi))
+        object.__setattr__(self, "cutmix", (cp, fmin, fmax))
+
+
+def elastic_lattice(h: int, w: int, pitch: float) -> Tuple[int, int]:
+    """``(gy, gx)``: rows and columns of the node lattice an h x w window needs at ``pitch`` pixels between nodes -- the cell of the
+    last pixel, ``floor((h - 1) / pitch)``, plus the four nodes the cubic B-spline reads from there."""
+    if h <= 0 or w <= 0 or not pitch >= 4:
+        raise ValueError("elastic_lattice: h, w must be positive and pitch at least 4")
+    return int(math.floor((h - 1) / pitch)) + 4, int(math.floor((w - 1) / pitch)) + 4
+
+
+def deform_entries(mix_from, ry0, ry1, rx0, rx1, nodes_off, gy, gx, inv_pitch, sigma, k0, k1) -> torch.Tensor:
+    """The (n, 16) int32 deform entry array of the deforming kernels (module docstring) from per-sample sequences; ``inv_pitch`` and
+    ``sigma`` are rounded once to fp32, the keys ``k0``, ``k1`` in [0, 2^32) stored by their bits."""
+    n = len(mix_from)
+    e = np.zeros((n, 16), dtype=np.int32)
+    for col, v in enumerate((mix_from, ry0, ry1, rx0, rx1, nodes_off, gy, gx)):
+        e[:, col] = np.asarray(v, dtype=np.int64)
+    e[:, 8] = np.asarray(inv_pitch, dtype=np.float64).astype(np.float32).view(np.int32)
+    e[:, 9] = np.asarray(sigma, dtype=np.float64).astype(np.float32).view(np.int32)
+    e[:, 10] = np.asarray(k0, dtype=np.int64).astype(np.uint32).view(np.int32)
+    e[:, 11] = np.asarray(k1, dtype=np.int64).astype(np.uint32).view(np.int32)
+    return torch.from_numpy(e)
+
+
+class DeformedPlan(NamedTuple):
+    order: torch.Tensor                 # as AugmentedPlan
+    table: torch.Tensor
+    entries: torch.Tensor
+    batches: List[Tuple[int, int]]
+    window: Tuple[int, int]
+    warped: List[bool]
+    deform: torch.Tensor                # (m, 16) int32: the deform entries (mix_from is an index INSIDE the sample's batch)
+    nodes: Optional[torch.Tensor]       # flat fp32 node table (nodes_off counts from its start), or None
+    deformed: List[bool]                # per batch: some sample needs the deforming kernels
+
+
+def plan_epoch_deformed(n: int, batch_size: int, frame: Tuple[int, int], channels: int, augment: Optional[CubeAugment] = None,
+                        deform: Optional[CubeDeform] = None, patch=None, shuffle: bool = True, random_crop: bool = False,
+                        flips: bool = False, drop_last: bool = False, generator: Optional[torch.Generator] = None) -> DeformedPlan:
+    """``plan_epoch_augmented`` plus the deformation draws of the module docstring (a pure host function).  Order, table, entries
+    and ``warped`` are ``plan_epoch_augmented``'s for the same generator state."""
+    dfm = CubeDeform() if deform is None else deform
+    plan = plan_epoch_augmented(n, batch_size, frame, channels, augment, patch, shuffle, random_crop, flips, drop_last, generator)
+    h, w = plan.window
+    r = [torch.rand(n, dtype=torch.float64, generator=generator).numpy() for _ in range(7)]
+    keys = torch.randint(0, 2 ** 32, (n, 2), dtype=torch.int64, generator=generator).numpy()
+    ep, esigma, pitch = dfm.elastic
+    m = plan.table.shape[0]
+    nodes, gy, gx = None, 0, 0
+    if ep > 0 and esigma > 0:
+        gy, gx = elastic_lattice(h, w, pitch)
+        nodes = (torch.randn(n, gy, gx, 2, dtype=torch.float64, generator=generator) * esigma).to(torch.float32)[:m].reshape(-1).contiguous()
+    elastic = (r[0] < ep) & (nodes is not None)
+    sigma = dfm.noise[0] + r[1] * (dfm.noise[1] - dfm.noise[0])
+    cp, fmin, fmax = dfm.cutmix
+    cut = r[2] < cp
+    rh = np.clip(np.round((fmin + r[3] * (fmax - fmin)) * h), 1, h).astype(np.int64)
+    rw = np.clip(np.round((fmin + r[4] * (fmax - fmin)) * w), 1, w).astype(np.int64)
+    ry0 = np.minimum(np.floor(r[5] * (h - rh + 1)).astype(np.int64), h - rh)
+    rx0 = np.minimum(np.floor(r[6] * (w - rw + 1)).astype(np.int64), w - rw)
+    mix_from = np.full(n, -1, dtype=np.int64)
+    for s, e in plan.batches:
+        if e - s > 1:
+            j = np.arange(e - s)
+            mix_from[s:e] = np.where(cut[s:e], (j - 1) % (e - s), -1)
+    on = mix_from >= 0
+    off = np.where(elastic, np.arange(n, dtype=np.int64) * (2 * gy * gx), -1)
+    d = deform_entries(mix_from[:m], np.where(on, ry0, 0)[:m], np.where(on, ry0 + rh, 0)[:m], np.where(on, rx0, 0)[:m],
+                       np.where(on, rx0 + rw, 0)[:m], off[:m], np.where(elastic, gy, 0)[:m], np.where(elastic, gx, 0)[:m],
+                       np.where(elastic, 1.0 / pitch, 0.0)[:m], sigma[:m], keys[:m, 0], keys[:m, 1])
+    needs = elastic | (sigma > 0) | on
+    deformed = [bool(needs[s:e].any()) for s, e in plan.batches]
+    return DeformedPlan(plan.order, plan.table, plan.entries, plan.batches, plan.window, plan.warped, d, nodes, deformed)
+
+
 class CubeCache:
     def __init__(self, capacity: int, height: int, width: int, bands: int, hsi_lo: int = 0, hsi_hi: Optional[int] = None,
                  device="cuda:0", store_dtype=torch.float32, unsqueeze_hsi: bool = True, out_slots: int = 2):
@@ -317,6 +452,7 @@ class CubeCache:
         self._staged: Optional[torch.cuda.Event] = None
         self._out: List[torch.Tensor] = []
         self._mout: List[torch.Tensor] = []
+        self._fout: List[Optional[torch.Tensor]] = []        # the elastic field of every output slot: (N, h, w, 2), allocated on first use
         self._out_shape = (0, 0, 0)     # (N allocated, h, w)
         self._out_stream: List[Optional[torch.cuda.Stream]] = []
         self._consumed: List[Optional[torch.cuda.Event]] = []
@@ -396,6 +532,7 @@ class CubeCache:
             # pad channels are rewritten (as zeros, from the slots) by every gather: no fill here either
             self._out = [torch.empty((n, h, w, self.cs), dtype=torch.float32, device=self.device) for _ in range(self.out_slots)]
             self._mout = [torch.empty((n, 1, h, w), dtype=torch.float32, device=self.device) for _ in range(self.out_slots)]
+            self._fout = [None] * self.out_slots
             self._out_shape = (n, h, w)
             self._out_stream = [None] * self.out_slots
             self._consumed = [None] * self.out_slots
@@ -437,6 +574,30 @@ class CubeCache:
             _lib.call("hpri_mask_warp", _p(self._masks), self.capacity, self.H, self.W, ep, n, h, w, _p(self._mout[k]), s)
         return self._hand_out(k, slots)
 
+    def _deform(self, entries_ptr: int, deform_ptr: int, nodes: Optional[torch.Tensor], lattice: bool, slots: Sequence[int], h: int,
+                w: int) -> dict:
+        """``_warp`` through the deforming kernels: ``deform_ptr`` points at ``len(slots)`` 64-byte deform entries on the device
+        beside the warp entries at ``entries_ptr``; ``nodes`` is the device node table their ``nodes_off`` count into.  With
+        ``lattice`` (some sample of the batch has one) the field of the output slot is built first; otherwise that launch is
+        skipped and the kernels get a null field."""
+        n = len(slots)
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            k = self._take_slot(n, h, w, cur)
+            s = ctypes.c_void_p(cur.cuda_stream)
+            ep, dp = ctypes.c_void_p(entries_ptr), ctypes.c_void_p(deform_ptr)
+            fp = ctypes.c_void_p(0)
+            if lattice:
+                if self._fout[k] is None:
+                    self._fout[k] = torch.empty((self._out_shape[0], h, w, 2), dtype=torch.float32, device=self.device)
+                fp = _p(self._fout[k])
+                _lib.call("hpri_elastic_field", _p(nodes) if nodes is not None else ctypes.c_void_p(0),
+                          nodes.numel() if nodes is not None else 0, dp, n, h, w, fp, s)
+            _lib.call("hpri_cube_deform", _p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs, self.C, ep,
+                      dp, fp, n, h, w, _p(self._out[k]), s)
+            _lib.call("hpri_mask_deform", _p(self._masks), self.capacity, self.H, self.W, ep, dp, fp, n, h, w, _p(self._mout[k]), s)
+        return self._hand_out(k, slots)
+
     def _hand_out(self, k: int, slots: Sequence[int]) -> dict:
         n = len(slots)
         x = self._out[k][:n, :, :, :self.C].permute(0, 3, 1, 2)        # logical (N,C,h,w), channels-last strides
@@ -452,7 +613,8 @@ class CubeCache:
                 raise IndexError(f"CubeCache: slot {i} is empty or out of range")
 
     def batch(self, indices: Sequence[int], top=None, left=None, flip_h=None, flip_w=None, patch=None, angle=None, zoom=None,
-              shift=None, gain=None, offset=None, band_drop=None, _force_warp: bool = False) -> dict:
+              shift=None, gain=None, offset=None, band_drop=None, _force_warp: bool = False, elastic=None, noise=None, cutmix=None,
+              _force_deform: bool = False) -> dict:
         """``{'image', 'mask', 'index'}`` for the cached cubes ``indices``: a window of ``patch`` (the whole frame by
         default) at ``top`` / ``left`` (per sample or one value; default: centred), flipped along rows (``flip_h``) and
         columns (``flip_w``).  Uploads a table of 16 bytes per sample; ``epoch()`` is the path without any copy.
@@ -460,7 +622,14 @@ class CubeCache:
         Augmentation, each per sample or one value for all (module docstring): ``angle`` in degrees, ``zoom`` (above 1
         magnifies), ``shift`` = ``(dx, dy)`` pixels added to the window centre, ``gain``, ``offset``, ``band_drop`` =
         ``(first, count)`` bands written as zeros.  A batch in which every sample is neutral takes the plain gather (the
-        same bits as without these arguments); any other one the warp kernels, with 64 bytes per sample uploaded."""
+        same bits as without these arguments); any other one the warp kernels, with 64 bytes per sample uploaded.
+
+        Deformation (module docstring): ``elastic`` = ``(nodes, pitch)`` with ``nodes`` an (n, gy, gx, 2) array of (dx, dy) node
+        displacements in output pixels (``elastic_lattice`` gives gy, gx) -- one lattice per sample --, ``noise`` = ``(sigma, k0, k1)``
+        and ``cutmix`` = ``(from, ry0, ry1, rx0, rx1)``, each per sample or one tuple for all; ``from`` is an index into ``indices``
+        (-1: none), and the kernels clamp the rectangle into the window.  With neutral values (no lattice, no sigma above 0, no
+        ``from`` inside the batch) the path and the bits are those without these arguments; otherwise the deforming kernels run,
+        with 128 bytes per sample and the lattices uploaded."""
         idx = [int(i) for i in indices]
         n = len(idx)
         if n == 0:
@@ -500,6 +669,37 @@ class CubeCache:
                 raise ValueError(f"CubeCache.batch: band_drop {(lo_, n_)} leaves the {self.C} bands")
         neutral = all(a == 0 and z == 1 and s_ == [0.0, 0.0] and g_ == 1 and o_ == 0 and d_[1] == 0
                       for a, z, s_, g_, o_, d_ in zip(angles, zooms, shifts, gains, offsets, drops))
+        nz = per_sample_f(noise, [0.0, 0.0, 0.0], 3)
+        cm = per_sample_f(cutmix, [-1.0, 0.0, 0.0, 0.0, 0.0], 5)
+        if any(k_ != int(k_) or not 0 <= k_ < 2 ** 32 for z_ in nz for k_ in z_[1:]):
+            raise ValueError("CubeCache.batch: noise keys must be whole numbers in [0, 2^32)")
+        if any(v_ != int(v_) or abs(v_) >= 2 ** 31 for c_ in cm for v_ in c_):
+            raise ValueError("CubeCache.batch: cutmix takes whole numbers (from, ry0, ry1, rx0, rx1)")
+        mixes = [0 <= c_[0] < n and c_[0] != j and max(c_[1], 0) < min(c_[2], h) and max(c_[3], 0) < min(c_[4], w) for j, c_ in enumerate(cm)]
+        if _force_deform or elastic is not None or any(z_[0] > 0 for z_ in nz) or any(mixes):
+            nodes, gy, gx, inv_pitch = None, 0, 0, 0.0
+            if elastic is not None:
+                nd, pitch = elastic
+                nodes = torch.as_tensor(np.asarray(nd.tolist() if hasattr(nd, "tolist") else nd, dtype=np.float64), dtype=torch.float32)
+                if nodes.dim() != 4 or nodes.shape[0] != n or nodes.shape[3] != 2 or not bool(torch.isfinite(nodes).all()) or not float(pitch) >= 4:
+                    raise ValueError("CubeCache.batch: elastic takes ((n, gy, gx, 2) finite node displacements, pitch >= 4)")
+                if tuple(nodes.shape[1:3]) != elastic_lattice(h, w, float(pitch)):
+                    raise ValueError(f"CubeCache.batch: a {h}x{w} window at pitch {pitch} needs a lattice of {elastic_lattice(h, w, float(pitch))}, "
+                                     f"got {tuple(nodes.shape[1:3])}")
+                gy, gx, inv_pitch = int(nodes.shape[1]), int(nodes.shape[2]), 1.0 / float(pitch)
+                nodes = nodes.reshape(-1).contiguous().to(self.device)
+            cell = 2 * gy * gx
+            both = torch.cat([
+                warp_entries(idx, tops, lefts, fhs, fws, (h, w), angles, zooms, [s_[0] for s_ in shifts], [s_[1] for s_ in shifts],
+                             gains, offsets, [int(d_[0]) for d_ in drops], [int(d_[1]) for d_ in drops]),
+                deform_entries([int(c_[0]) for c_ in cm], [int(c_[1]) for c_ in cm], [int(c_[2]) for c_ in cm], [int(c_[3]) for c_ in cm],
+                               [int(c_[4]) for c_ in cm], [j * cell if nodes is not None else -1 for j in range(n)], [gy] * n, [gx] * n,
+                               [inv_pitch] * n, [z_[0] for z_ in nz], [int(z_[1]) for z_ in nz], [int(z_[2]) for z_ in nz])]).to(self.device)
+            out = self._deform(both.data_ptr(), both.data_ptr() + 64 * n, nodes, nodes is not None, idx, h, w)
+            both.record_stream(torch.cuda.current_stream(self.device))
+            if nodes is not None:
+                nodes.record_stream(torch.cuda.current_stream(self.device))
+            return out
         if _force_warp or not neutral:
             entries = warp_entries(idx, tops, lefts, fhs, fws, (h, w), angles, zooms, [s_[0] for s_ in shifts], [s_[1] for s_ in shifts],
                                    gains, offsets, [int(d_[0]) for d_ in drops], [int(d_[1]) for d_ in drops]).to(self.device)
@@ -514,15 +714,21 @@ class CubeCache:
 
     def epoch(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None, patch=None,
               random_crop: bool = False, flips: bool = False, drop_last: bool = False,
-              augment: Optional[CubeAugment] = None) -> Iterator[dict]:
+              augment: Optional[CubeAugment] = None, deform: Optional[CubeDeform] = None) -> Iterator[dict]:
         """Iterate one epoch (``plan_epoch`` over the filled slots, which must be slots 0 .. len-1).  The plan is drawn and
         its table uploaded before the first batch; ``plan`` of the most recent call is kept as ``last_plan``.  With
         ``augment`` the plan is ``plan_epoch_augmented``'s (an ``AugmentedPlan``): its entries are uploaded beside the table,
-        and every batch it flags goes through the warp kernels, the others through the plain gather."""
+        and every batch it flags goes through the warp kernels, the others through the plain gather.  With ``deform`` the plan
+        is ``plan_epoch_deformed``'s (a ``DeformedPlan``; ``augment`` may be None): its deform entries and node table are uploaded
+        once as well, a batch it flags as ``deformed`` goes through the deforming kernels -- the field launch skipped, and a null
+        field passed, when no sample of the batch has a lattice --, the others as before."""
         n = len(self)
         if n == 0 or not all(self._filled[:n]):
             raise RuntimeError("CubeCache.epoch: fill slots 0 .. len-1 first")
-        if augment is None:
+        if deform is not None:
+            plan = plan_epoch_deformed(n, batch_size, (self.H, self.W), self.C, augment, deform, patch, shuffle, random_crop, flips,
+                                       drop_last, generator)
+        elif augment is None:
             plan = plan_epoch(n, batch_size, (self.H, self.W), patch, shuffle, random_crop, flips, drop_last, generator)
         else:
             plan = plan_epoch_augmented(n, batch_size, (self.H, self.W), self.C, augment, patch, shuffle, random_crop, flips,
@@ -537,13 +743,23 @@ class CubeCache:
         with torch.cuda.device(self.device):
             table = plan.table.pin_memory().to(self.device, non_blocking=True)     # once per epoch, asynchronous
             warped = getattr(plan, "warped", None)
-            entries = plan.entries.pin_memory().to(self.device, non_blocking=True) if warped and any(warped) else None
+            deformed = getattr(plan, "deformed", None)
+            entries = plan.entries.pin_memory().to(self.device, non_blocking=True) if warped and (any(warped) or any(deformed or ())) else None
+            dtable = nodes = lattice = None
+            if deformed and any(deformed):
+                dtable = plan.deform.pin_memory().to(self.device, non_blocking=True)
+                nodes = plan.nodes.pin_memory().to(self.device, non_blocking=True) if plan.nodes is not None else None
+                lattice = (plan.deform[:, 5] >= 0).tolist()
+        self._deform_tables = (dtable, nodes)
         self._table = table             # (alive until the next epoch's table replaces it, also when this iterator is dropped early)
         self._entries = entries
         order = plan.order.tolist()
         base = table.data_ptr()
         for b, (start, stop) in enumerate(plan.batches):
-            if entries is not None and warped[b]:
+            if dtable is not None and deformed[b]:
+                yield self._deform(entries.data_ptr() + 64 * start, dtable.data_ptr() + 64 * start, nodes, any(lattice[start:stop]),
+                                   order[start:stop], h, w)
+            elif entries is not None and warped[b]:
                 yield self._warp(entries.data_ptr() + 64 * start, order[start:stop], h, w)
             else:
                 yield self._gather(base + 16 * start, order[start:stop], h, w)

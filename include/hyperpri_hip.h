@@ -579,6 +579,43 @@ int hpri_cube_warp(const void* cache, int cache_dtype, int slots, int Hs, int Ws
 int hpri_mask_warp(const unsigned char* masks, int slots, int Hs, int Ws, const int* entries, int N, int h, int w, float* dst,
                    hipStream_t stream);
 
+/* ---- cube cache, deforming gather (cache_deform.hip; hyperpri_amd/cache.py: CubeDeform) -------------------
+ * The warp pair's pass with an elastic displacement field in the coordinate, Gaussian noise in the value and a CutMix rectangle
+ * that hands pixels to another sample of the batch.  Beside the warp entries a second record per sample:
+ * Deform entry: 64 bytes = 16 32-bit words per sample, in DEVICE memory, 16-byte aligned:
+ *     word 0 int32 mix_from (batch index in [0, N) of the sample that owns the rectangle's pixels; anything else, -1 included, or the
+ *     sample's own index: no CutMix) | 1..4 int32 ry0, ry1, rx0, rx1 (the rectangle [ry0,ry1) x [rx0,rx1) in window coordinates,
+ *     clamped into the window by the kernels; empty: none) | 5 int32 nodes_off (offset in floats of the sample's lattice in the node
+ *     table; negative: no elastic field) | 6, 7 int32 gy, gx (lattice rows, columns) | 8 fp32 inv_pitch (1 / node spacing in output
+ *     pixels) | 9 fp32 noise_sigma (applied only when > 0; NaN or negative: none) | 10, 11 uint32 k0, k1 (Philox key) | 12..15 reserved (0)
+ *   hpri_elastic_field  field[n, y, x, :] = (dx, dy) in output pixels, fp32: ty = y * inv_pitch, iy = clamp(floor ty, 0, gy - 4),
+ *                   fy = ty - iy (x alike), d = sum_a sum_b B_a(fy) B_b(fx) node[iy+a][ix+b] over 4 x 4 nodes of the sample's (gy, gx, 2)
+ *                   row-major lattice, uniform cubic B-spline: B0 = (1-f)^3/6, B1 = (3f^3 - 6f^2 + 4)/6, B2 = (-3f^3 + 3f^2 + 3f + 1)/6,
+ *                   B3 = f^3/6.  Exact +0 for a sample without a lattice, with gy < 4 or gx < 4, or whose
+ *                   [nodes_off, nodes_off + 2*gy*gx) does not lie inside [0, nodes_len) (the kernel decides: the launcher cannot see
+ *                   the entries).  nodes may be null when nodes_len is 0.
+ *   hpri_cube_deform / hpri_mask_deform  output pixel (y, x) of sample s: the owner o = mix_from[s] when CutMix is on for s and the
+ *                   pixel lies in its rectangle, else s (o's own CutMix words are ignored);
+ *                       u = (x + field[o,y,x,0]) - (w-1)/2,  v = (y + field[o,y,x,1]) - (h-1)/2        (field == NULL: zeros)
+ *                   then sx, sy, the sampling, gain, offset and band drop of hpri_cube_warp / hpri_mask_warp with o's WARP entry and
+ *                   the same clamps.  Cube: out = base = fmaf(gain, acc, offset), or fmaf(sigma, z, base) when sigma[s] > 0 -- noise and
+ *                   key are always those of s; dropped and pad channels stay exactly 0; the mask never sees noise.
+ *                   z: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) under the key
+ *                   (k0, k1) at the counter (lo32 e, hi32 e, 0, 0), e = (y*w + x) * (cs/4) + c0/4 in 64 bits; output words r0..r3 belong
+ *                   to channels c0..c0+3; pairs (r0, r1), (r2, r3) through Box-Muller: u = ((r >> 9) + 0.5f) * 2^-23,
+ *                   rad = sqrtf(-2 logf(u_a)), z_a = rad * cospif(2 u_b), z_b = rad * sinpif(2 u_b).
+ *   hpri_deform_noise_host  host only, no device: bits4 = the four Philox words, z4 = the four normals of counter e under (k0, k1)
+ *                   (either pointer may be null, not both) -- the generator of the kernel, through the shared csrc/deform_math.h.
+ * Argument errors -- a null pointer other than field, dtype, sizes, cs % 8, C outside (0, cs], h or w above 4096, the size products,
+ * 16-byte alignment of cache / dst / entries / deform / field (the node table: 8), nodes_len < 0 -- are reported before any launch. */
+int hpri_elastic_field(const float* nodes, long long nodes_len, const int* deform, int N, int h, int w, float* field,
+                       hipStream_t stream);
+int hpri_cube_deform(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, int C, const int* entries,
+                     const int* deform, const float* field, int N, int h, int w, float* dst, hipStream_t stream);
+int hpri_mask_deform(const unsigned char* masks, int slots, int Hs, int Ws, const int* entries, const int* deform,
+                     const float* field, int N, int h, int w, float* dst, hipStream_t stream);
+int hpri_deform_noise_host(unsigned int k0, unsigned int k1, unsigned long long e, unsigned int* bits4, float* z4);
+
 /* ---- colour-coded segmentation maps (segmap.hip; hyperpri_amd/evaluate.py) --------------------------------
  * The per-pixel arithmetic of eval_color_segmaps (PLTrainer.py:219-267) minus matplotlib: three bands of the image as a
  * gamma-corrected pseudo-RGB picture (:236-240, `img[hsi_rgb] ** (1 / 2.2)`), prediction and ground truth painted in the
