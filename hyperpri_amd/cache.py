@@ -68,7 +68,7 @@ quantity's stream), entry j again for the j-th sample served:
   9. ``run = min(1 + floor(r * max_run), max_run, C)``;   10. ``drop_lo = min(floor(r * (C - run + 1)), C - run)``.
 A batch in which no sample needs the warp (identity geometry, gain 1, offset 0, no drop) goes through the plain gather.
 
-Deformation (``CubeDeform``, ``plan_epoch_deformed``, csrc/cache_deform.hip) -- opt-in again; without it nothing above changes.
+Deformation (``CubeDeform``, ``plan_epoch_deformed``, csrc/cache_warp.hip, csrc/cache_deform.hip) -- opt-in again; without it nothing above changes.
 Elastic deformation, additive Gaussian noise and CutMix in the same pass.  Beside the warp entry a second 64-byte record per sample:
     ``[mix_from, ry0, ry1, rx0, rx1, nodes_off, gy, gx, inv_pitch, noise_sigma, k0, k1, 0, 0, 0, 0]``  (words 8, 9 hold fp32 bits)
   * elastic: a coarse lattice of random displacements (``(gy, gx, 2)`` fp32 = (dx, dy) in output pixels, nodes ``pitch`` pixels apart,
@@ -416,6 +416,94 @@ def plan_epoch_deformed(n: int, batch_size: int, frame: Tuple[int, int], channel
     return DeformedPlan(plan.order, plan.table, plan.entries, plan.batches, plan.window, plan.warped, d, nodes, deformed)
 
 
+class BatchPlan(NamedTuple):
+    path: str                           # "gather", "warp" or "deform": the kernels that serve the batch
+    window: Tuple[int, int]             # (h, w)
+    table: Optional[torch.Tensor]       # gather: (n, 4) int32 {slot, top, left, flags}
+    entries: Optional[torch.Tensor]     # warp, deform: (n, 16) int32 warp entries
+    deform: Optional[torch.Tensor]      # deform: (n, 16) int32 deform entries (nodes_off = j * 2 gy gx with a lattice, else -1)
+    nodes: Optional[torch.Tensor]       # deform with ``elastic``: the flat fp32 node table
+
+
+def plan_batch(indices: Sequence[int], frame: Tuple[int, int], channels: int, top=None, left=None, flip_h=None, flip_w=None, patch=None,
+               angle=None, zoom=None, shift=None, gain=None, offset=None, band_drop=None, elastic=None, noise=None, cutmix=None,
+               force_warp: bool = False, force_deform: bool = False) -> BatchPlan:
+    """The host half of ``CubeCache.batch`` (whose arguments these are; ``frame`` = (H, W) and ``channels`` = C of the cache; a pure
+    host function): one value per sample of everything, validated; which kernels serve the batch -- the deforming ones with a
+    lattice, a sigma above 0 or a CutMix partner inside the batch, else the warp pair when any sample is not neutral, else the
+    plain gather --; and the host tensors that path uploads."""
+    idx = [int(i) for i in indices]
+    n = len(idx)
+    if n == 0:
+        raise ValueError("CubeCache.batch: no indices")
+    H, W = frame
+    h, w = _hw(patch, H, W)
+
+    def per_sample(v, default):
+        if v is None:
+            return [default] * n
+        v = [int(e) for e in (v.tolist() if hasattr(v, "tolist") else v)] if hasattr(v, "__len__") else [int(v)] * n
+        if len(v) != n:
+            raise ValueError("CubeCache.batch: one value per sample")
+        return v
+    tops, lefts = per_sample(top, (H - h) // 2), per_sample(left, (W - w) // 2)
+    fhs, fws = per_sample(flip_h, 0), per_sample(flip_w, 0)
+    for t_, l_ in zip(tops, lefts):
+        if not (0 <= t_ <= H - h and 0 <= l_ <= W - w):
+            raise ValueError(f"CubeCache.batch: window {h}x{w} at ({t_}, {l_}) leaves the {H}x{W} frame")
+
+    def per_sample_f(v, default, width=1):
+        if v is None:
+            return [default] * n
+        a = np.asarray(v.tolist() if hasattr(v, "tolist") else v, dtype=np.float64)
+        if a.ndim == (width > 1):
+            a = np.broadcast_to(a, (n,) + a.shape)
+        if a.shape != ((n,) if width == 1 else (n, width)) or not np.isfinite(a).all():
+            raise ValueError("CubeCache.batch: one finite value per sample" if width == 1 else
+                             f"CubeCache.batch: one finite {width}-tuple per sample")
+        return a.tolist()
+    angles, zooms, shifts = per_sample_f(angle, 0.0), per_sample_f(zoom, 1.0), per_sample_f(shift, [0.0, 0.0], 2)
+    gains, offsets, drops = per_sample_f(gain, 1.0), per_sample_f(offset, 0.0), per_sample_f(band_drop, [0.0, 0.0], 2)
+    if any(not 1 / 16 <= z <= 16 for z in zooms):
+        raise ValueError("CubeCache.batch: zoom must lie in [1/16, 16]")
+    for lo_, n_ in drops:
+        if lo_ != int(lo_) or n_ != int(n_) or lo_ < 0 or n_ < 0 or lo_ + n_ > channels:
+            raise ValueError(f"CubeCache.batch: band_drop {(lo_, n_)} leaves the {channels} bands")
+    neutral = all(a == 0 and z == 1 and s_ == [0.0, 0.0] and g_ == 1 and o_ == 0 and d_[1] == 0
+                  for a, z, s_, g_, o_, d_ in zip(angles, zooms, shifts, gains, offsets, drops))
+    nz = per_sample_f(noise, [0.0, 0.0, 0.0], 3)
+    cm = per_sample_f(cutmix, [-1.0, 0.0, 0.0, 0.0, 0.0], 5)
+    if any(k_ != int(k_) or not 0 <= k_ < 2 ** 32 for z_ in nz for k_ in z_[1:]):
+        raise ValueError("CubeCache.batch: noise keys must be whole numbers in [0, 2^32)")
+    if any(v_ != int(v_) or abs(v_) >= 2 ** 31 for c_ in cm for v_ in c_):
+        raise ValueError("CubeCache.batch: cutmix takes whole numbers (from, ry0, ry1, rx0, rx1)")
+    mixes = [0 <= c_[0] < n and c_[0] != j and max(c_[1], 0) < min(c_[2], h) and max(c_[3], 0) < min(c_[4], w) for j, c_ in enumerate(cm)]
+    deformed = force_deform or elastic is not None or any(z_[0] > 0 for z_ in nz) or any(mixes)
+    if not (deformed or force_warp or not neutral):
+        rows = [[i, t_, l_, (1 if a else 0) | (2 if b else 0)] for i, t_, l_, a, b in zip(idx, tops, lefts, fhs, fws)]
+        return BatchPlan("gather", (h, w), torch.tensor(rows, dtype=torch.int32), None, None, None)
+    entries = warp_entries(idx, tops, lefts, fhs, fws, (h, w), angles, zooms, [s_[0] for s_ in shifts], [s_[1] for s_ in shifts],
+                           gains, offsets, [int(d_[0]) for d_ in drops], [int(d_[1]) for d_ in drops])
+    if not deformed:
+        return BatchPlan("warp", (h, w), None, entries, None, None)
+    nodes, gy, gx, inv_pitch = None, 0, 0, 0.0
+    if elastic is not None:
+        nd, pitch = elastic
+        nodes = torch.as_tensor(np.asarray(nd.tolist() if hasattr(nd, "tolist") else nd, dtype=np.float64), dtype=torch.float32)
+        if nodes.dim() != 4 or nodes.shape[0] != n or nodes.shape[3] != 2 or not bool(torch.isfinite(nodes).all()) or not float(pitch) >= 4:
+            raise ValueError("CubeCache.batch: elastic takes ((n, gy, gx, 2) finite node displacements, pitch >= 4)")
+        if tuple(nodes.shape[1:3]) != elastic_lattice(h, w, float(pitch)):
+            raise ValueError(f"CubeCache.batch: a {h}x{w} window at pitch {pitch} needs a lattice of {elastic_lattice(h, w, float(pitch))}, "
+                             f"got {tuple(nodes.shape[1:3])}")
+        gy, gx, inv_pitch = int(nodes.shape[1]), int(nodes.shape[2]), 1.0 / float(pitch)
+        nodes = nodes.reshape(-1).contiguous()
+    cell = 2 * gy * gx
+    deform = deform_entries([int(c_[0]) for c_ in cm], [int(c_[1]) for c_ in cm], [int(c_[2]) for c_ in cm], [int(c_[3]) for c_ in cm],
+                            [int(c_[4]) for c_ in cm], [j * cell if nodes is not None else -1 for j in range(n)], [gy] * n, [gx] * n,
+                            [inv_pitch] * n, [z_[0] for z_ in nz], [int(z_[1]) for z_ in nz], [int(z_[2]) for z_ in nz])
+    return BatchPlan("deform", (h, w), None, entries, deform, nodes)
+
+
 class CubeCache:
     def __init__(self, capacity: int, height: int, width: int, bands: int, hsi_lo: int = 0, hsi_hi: Optional[int] = None,
                  device="cuda:0", store_dtype=torch.float32, unsqueeze_hsi: bool = True, out_slots: int = 2):
@@ -549,63 +637,54 @@ class CubeCache:
         self._out_stream[k] = cur
         return k
 
-    def _gather(self, table_ptr: int, slots: Sequence[int], h: int, w: int) -> dict:
+    def _launch(self, slots: Sequence[int], window: Tuple[int, int], table: int = 0, entries: int = 0, deform: int = 0,
+                nodes: Optional[torch.Tensor] = None, lattice: bool = False, transposed: bool = False) -> dict:
+        """Fill the next output slot with the ``window`` = (h, w) of the cubes ``slots`` on the current stream and hand it out.  The
+        arguments are device addresses of ``len(slots)`` rows: with ``deform`` (64-byte deform entries beside the warp entries at
+        ``entries``; ``nodes`` is the device node table their ``nodes_off`` count into) the deforming kernels run, else with
+        ``entries`` the warp kernel pair, else the plain gather with the 16-byte rows at ``table``.  With ``lattice`` (some sample of
+        the batch has one) the field of the output slot is built first; otherwise that launch is skipped and the deforming kernels
+        get a null field.  ``transposed``: the window is (W, H) of whole frames.  It has as many pixels as the frame, so it is
+        written into the (H, W) output buffers themselves, read as (n, W, H, cs): ``_take_slot`` sees the frame's shape, and
+        alternating between the two orientations allocates nothing."""
         n = len(slots)
+        h, w = window
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream(self.device)
-            k = self._take_slot(n, h, w, cur)
+            k = self._take_slot(n, *((w, h) if transposed else (h, w)), cur)
             s = ctypes.c_void_p(cur.cuda_stream)
-            tp = ctypes.c_void_p(table_ptr)
-            _lib.call("hpri_cube_gather", _p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs, tp, n,
-                      h, w, _p(self._out[k]), s)
-            _lib.call("hpri_mask_gather", _p(self._masks), self.capacity, self.H, self.W, tp, n, h, w, _p(self._mout[k]), s)
-        return self._hand_out(k, slots)
+            tp, ep, dp = ctypes.c_void_p(table), ctypes.c_void_p(entries), ctypes.c_void_p(deform)
+            cube = (_p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs)
+            mask = (_p(self._masks), self.capacity, self.H, self.W)
+            out = (n, h, w, _p(self._out[k]), s)
+            mout = (n, h, w, _p(self._mout[k]), s)
+            if deform:
+                fp = ctypes.c_void_p(0)
+                if lattice:
+                    if self._fout[k] is None:
+                        self._fout[k] = torch.empty((self._out_shape[0], h, w, 2), dtype=torch.float32, device=self.device)
+                    fp = _p(self._fout[k])
+                    _lib.call("hpri_elastic_field", _p(nodes) if nodes is not None else ctypes.c_void_p(0),
+                              nodes.numel() if nodes is not None else 0, dp, n, h, w, fp, s)
+                _lib.call("hpri_cube_deform", *cube, self.C, ep, dp, fp, *out)
+                _lib.call("hpri_mask_deform", *mask, ep, dp, fp, *mout)
+            elif entries:
+                _lib.call("hpri_cube_warp", *cube, self.C, ep, *out)
+                _lib.call("hpri_mask_warp", *mask, ep, *mout)
+            else:
+                _lib.call("hpri_cube_gather", *cube, tp, *out)
+                _lib.call("hpri_mask_gather", *mask, tp, *mout)
+        return self._hand_out(k, slots, window)
 
-    def _warp(self, entries_ptr: int, slots: Sequence[int], h: int, w: int) -> dict:
-        """``_gather`` through the warp kernel pair: ``entries_ptr`` points at ``len(slots)`` 64-byte entries on the device."""
+    def _hand_out(self, k: int, slots: Sequence[int], window: Tuple[int, int]) -> dict:
         n = len(slots)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            k = self._take_slot(n, h, w, cur)
-            s = ctypes.c_void_p(cur.cuda_stream)
-            ep = ctypes.c_void_p(entries_ptr)
-            _lib.call("hpri_cube_warp", _p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs, self.C, ep,
-                      n, h, w, _p(self._out[k]), s)
-            _lib.call("hpri_mask_warp", _p(self._masks), self.capacity, self.H, self.W, ep, n, h, w, _p(self._mout[k]), s)
-        return self._hand_out(k, slots)
-
-    def _deform(self, entries_ptr: int, deform_ptr: int, nodes: Optional[torch.Tensor], lattice: bool, slots: Sequence[int], h: int,
-                w: int) -> dict:
-        """``_warp`` through the deforming kernels: ``deform_ptr`` points at ``len(slots)`` 64-byte deform entries on the device
-        beside the warp entries at ``entries_ptr``; ``nodes`` is the device node table their ``nodes_off`` count into.  With
-        ``lattice`` (some sample of the batch has one) the field of the output slot is built first; otherwise that launch is
-        skipped and the kernels get a null field."""
-        n = len(slots)
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            k = self._take_slot(n, h, w, cur)
-            s = ctypes.c_void_p(cur.cuda_stream)
-            ep, dp = ctypes.c_void_p(entries_ptr), ctypes.c_void_p(deform_ptr)
-            fp = ctypes.c_void_p(0)
-            if lattice:
-                if self._fout[k] is None:
-                    self._fout[k] = torch.empty((self._out_shape[0], h, w, 2), dtype=torch.float32, device=self.device)
-                fp = _p(self._fout[k])
-                _lib.call("hpri_elastic_field", _p(nodes) if nodes is not None else ctypes.c_void_p(0),
-                          nodes.numel() if nodes is not None else 0, dp, n, h, w, fp, s)
-            _lib.call("hpri_cube_deform", _p(self._cubes), _DT[self.store_dtype], self.capacity, self.H, self.W, self.cs, self.C, ep,
-                      dp, fp, n, h, w, _p(self._out[k]), s)
-            _lib.call("hpri_mask_deform", _p(self._masks), self.capacity, self.H, self.W, ep, dp, fp, n, h, w, _p(self._mout[k]), s)
-        return self._hand_out(k, slots)
-
-    def _hand_out(self, k: int, slots: Sequence[int]) -> dict:
-        n = len(slots)
-        x = self._out[k][:n, :, :, :self.C].permute(0, 3, 1, 2)        # logical (N,C,h,w), channels-last strides
+        h, w = window
+        x = self._out[k][:n].view(n, h, w, self.cs)[:, :, :, :self.C].permute(0, 3, 1, 2)       # logical (N,C,h,w), channels-last strides
         if self.unsqueeze:
             x = x.unsqueeze(1)                                          # (N,1,C,h,w) as dataset.py:269-270
         x._hpri_zero_padded = True
         x._hpri_slot = k
-        return {'image': x, 'mask': self._mout[k][:n], 'index': [self._names[i] for i in slots]}
+        return {'image': x, 'mask': self._mout[k][:n].view(n, 1, h, w), 'index': [self._names[i] for i in slots]}
 
     def _check_filled(self, slots: Sequence[int]) -> None:
         for i in slots:
@@ -631,85 +710,23 @@ class CubeCache:
         ``from`` inside the batch) the path and the bits are those without these arguments; otherwise the deforming kernels run,
         with 128 bytes per sample and the lattices uploaded."""
         idx = [int(i) for i in indices]
-        n = len(idx)
-        if n == 0:
-            raise ValueError("CubeCache.batch: no indices")
         self._check_filled(idx)
-        h, w = _hw(patch, self.H, self.W)
-
-        def per_sample(v, default):
-            if v is None:
-                return [default] * n
-            v = [int(e) for e in (v.tolist() if hasattr(v, "tolist") else v)] if hasattr(v, "__len__") else [int(v)] * n
-            if len(v) != n:
-                raise ValueError("CubeCache.batch: one value per sample")
-            return v
-        tops, lefts = per_sample(top, (self.H - h) // 2), per_sample(left, (self.W - w) // 2)
-        fhs, fws = per_sample(flip_h, 0), per_sample(flip_w, 0)
-        for t_, l_ in zip(tops, lefts):
-            if not (0 <= t_ <= self.H - h and 0 <= l_ <= self.W - w):
-                raise ValueError(f"CubeCache.batch: window {h}x{w} at ({t_}, {l_}) leaves the {self.H}x{self.W} frame")
-
-        def per_sample_f(v, default, width=1):
-            if v is None:
-                return [default] * n
-            a = np.asarray(v.tolist() if hasattr(v, "tolist") else v, dtype=np.float64)
-            if a.ndim == (width > 1):
-                a = np.broadcast_to(a, (n,) + a.shape)
-            if a.shape != ((n,) if width == 1 else (n, width)) or not np.isfinite(a).all():
-                raise ValueError("CubeCache.batch: one finite value per sample" if width == 1 else
-                                 f"CubeCache.batch: one finite {width}-tuple per sample")
-            return a.tolist()
-        angles, zooms, shifts = per_sample_f(angle, 0.0), per_sample_f(zoom, 1.0), per_sample_f(shift, [0.0, 0.0], 2)
-        gains, offsets, drops = per_sample_f(gain, 1.0), per_sample_f(offset, 0.0), per_sample_f(band_drop, [0.0, 0.0], 2)
-        if any(not 1 / 16 <= z <= 16 for z in zooms):
-            raise ValueError("CubeCache.batch: zoom must lie in [1/16, 16]")
-        for lo_, n_ in drops:
-            if lo_ != int(lo_) or n_ != int(n_) or lo_ < 0 or n_ < 0 or lo_ + n_ > self.C:
-                raise ValueError(f"CubeCache.batch: band_drop {(lo_, n_)} leaves the {self.C} bands")
-        neutral = all(a == 0 and z == 1 and s_ == [0.0, 0.0] and g_ == 1 and o_ == 0 and d_[1] == 0
-                      for a, z, s_, g_, o_, d_ in zip(angles, zooms, shifts, gains, offsets, drops))
-        nz = per_sample_f(noise, [0.0, 0.0, 0.0], 3)
-        cm = per_sample_f(cutmix, [-1.0, 0.0, 0.0, 0.0, 0.0], 5)
-        if any(k_ != int(k_) or not 0 <= k_ < 2 ** 32 for z_ in nz for k_ in z_[1:]):
-            raise ValueError("CubeCache.batch: noise keys must be whole numbers in [0, 2^32)")
-        if any(v_ != int(v_) or abs(v_) >= 2 ** 31 for c_ in cm for v_ in c_):
-            raise ValueError("CubeCache.batch: cutmix takes whole numbers (from, ry0, ry1, rx0, rx1)")
-        mixes = [0 <= c_[0] < n and c_[0] != j and max(c_[1], 0) < min(c_[2], h) and max(c_[3], 0) < min(c_[4], w) for j, c_ in enumerate(cm)]
-        if _force_deform or elastic is not None or any(z_[0] > 0 for z_ in nz) or any(mixes):
-            nodes, gy, gx, inv_pitch = None, 0, 0, 0.0
-            if elastic is not None:
-                nd, pitch = elastic
-                nodes = torch.as_tensor(np.asarray(nd.tolist() if hasattr(nd, "tolist") else nd, dtype=np.float64), dtype=torch.float32)
-                if nodes.dim() != 4 or nodes.shape[0] != n or nodes.shape[3] != 2 or not bool(torch.isfinite(nodes).all()) or not float(pitch) >= 4:
-                    raise ValueError("CubeCache.batch: elastic takes ((n, gy, gx, 2) finite node displacements, pitch >= 4)")
-                if tuple(nodes.shape[1:3]) != elastic_lattice(h, w, float(pitch)):
-                    raise ValueError(f"CubeCache.batch: a {h}x{w} window at pitch {pitch} needs a lattice of {elastic_lattice(h, w, float(pitch))}, "
-                                     f"got {tuple(nodes.shape[1:3])}")
-                gy, gx, inv_pitch = int(nodes.shape[1]), int(nodes.shape[2]), 1.0 / float(pitch)
-                nodes = nodes.reshape(-1).contiguous().to(self.device)
-            cell = 2 * gy * gx
-            both = torch.cat([
-                warp_entries(idx, tops, lefts, fhs, fws, (h, w), angles, zooms, [s_[0] for s_ in shifts], [s_[1] for s_ in shifts],
-                             gains, offsets, [int(d_[0]) for d_ in drops], [int(d_[1]) for d_ in drops]),
-                deform_entries([int(c_[0]) for c_ in cm], [int(c_[1]) for c_ in cm], [int(c_[2]) for c_ in cm], [int(c_[3]) for c_ in cm],
-                               [int(c_[4]) for c_ in cm], [j * cell if nodes is not None else -1 for j in range(n)], [gy] * n, [gx] * n,
-                               [inv_pitch] * n, [z_[0] for z_ in nz], [int(z_[1]) for z_ in nz], [int(z_[2]) for z_ in nz])]).to(self.device)
-            out = self._deform(both.data_ptr(), both.data_ptr() + 64 * n, nodes, nodes is not None, idx, h, w)
-            both.record_stream(torch.cuda.current_stream(self.device))
-            if nodes is not None:
-                nodes.record_stream(torch.cuda.current_stream(self.device))
-            return out
-        if _force_warp or not neutral:
-            entries = warp_entries(idx, tops, lefts, fhs, fws, (h, w), angles, zooms, [s_[0] for s_ in shifts], [s_[1] for s_ in shifts],
-                                   gains, offsets, [int(d_[0]) for d_ in drops], [int(d_[1]) for d_ in drops]).to(self.device)
-            out = self._warp(entries.data_ptr(), idx, h, w)
-            entries.record_stream(torch.cuda.current_stream(self.device))
-            return out
-        rows = [[i, t_, l_, (1 if a else 0) | (2 if b else 0)] for i, t_, l_, a, b in zip(idx, tops, lefts, fhs, fws)]
-        table = torch.tensor(rows, dtype=torch.int32).to(self.device)
-        out = self._gather(table.data_ptr(), idx, h, w)
-        table.record_stream(torch.cuda.current_stream(self.device))
+        plan = plan_batch(idx, (self.H, self.W), self.C, top, left, flip_h, flip_w, patch, angle, zoom, shift, gain, offset, band_drop,
+                          elastic, noise, cutmix, force_warp=_force_warp, force_deform=_force_deform)
+        nodes = plan.nodes.to(self.device) if plan.nodes is not None else None
+        if plan.path == "deform":
+            rows = torch.cat([plan.entries, plan.deform]).to(self.device)
+            out = self._launch(idx, plan.window, entries=rows.data_ptr(), deform=rows.data_ptr() + 64 * len(idx), nodes=nodes,
+                               lattice=nodes is not None)
+        elif plan.path == "warp":
+            rows = plan.entries.to(self.device)
+            out = self._launch(idx, plan.window, entries=rows.data_ptr())
+        else:
+            rows = plan.table.to(self.device)
+            out = self._launch(idx, plan.window, table=rows.data_ptr())
+        rows.record_stream(torch.cuda.current_stream(self.device))
+        if nodes is not None:
+            nodes.record_stream(torch.cuda.current_stream(self.device))
         return out
 
     def epoch(self, batch_size: int, shuffle: bool = True, generator: Optional[torch.Generator] = None, patch=None,
@@ -739,7 +756,6 @@ class CubeCache:
     def _serve(self, plan) -> Iterator[dict]:
         if not plan.batches:
             return
-        h, w = plan.window
         with torch.cuda.device(self.device):
             table = plan.table.pin_memory().to(self.device, non_blocking=True)     # once per epoch, asynchronous
             warped = getattr(plan, "warped", None)
@@ -756,36 +772,16 @@ class CubeCache:
         order = plan.order.tolist()
         base = table.data_ptr()
         for b, (start, stop) in enumerate(plan.batches):
+            slots = order[start:stop]
             if dtable is not None and deformed[b]:
-                yield self._deform(entries.data_ptr() + 64 * start, dtable.data_ptr() + 64 * start, nodes, any(lattice[start:stop]),
-                                   order[start:stop], h, w)
+                yield self._launch(slots, plan.window, entries=entries.data_ptr() + 64 * start, deform=dtable.data_ptr() + 64 * start,
+                                   nodes=nodes, lattice=any(lattice[start:stop]))
             elif entries is not None and warped[b]:
-                yield self._warp(entries.data_ptr() + 64 * start, order[start:stop], h, w)
+                yield self._launch(slots, plan.window, entries=entries.data_ptr() + 64 * start)
             else:
-                yield self._gather(base + 16 * start, order[start:stop], h, w)
+                yield self._launch(slots, plan.window, table=base + 16 * start)
 
     # ---- views for test-time augmentation (hyperpri_amd/tta.py) -----------------------------------------------------
-    def _warp_transposed(self, entries_ptr: int, slots: Sequence[int]) -> dict:
-        """``_warp`` for a (W, H) window of whole frames.  The window has as many pixels as the frame, so it is written into
-        the (H, W) output buffers themselves, read as (n, W, H, cs): ``_take_slot`` sees the frame's shape, and alternating
-        between the two orientations allocates nothing.  Slot rotation and stream ordering are ``_warp``'s."""
-        n = len(slots)
-        H, W = self.H, self.W
-        with torch.cuda.device(self.device):
-            cur = torch.cuda.current_stream(self.device)
-            k = self._take_slot(n, H, W, cur)
-            s = ctypes.c_void_p(cur.cuda_stream)
-            ep = ctypes.c_void_p(entries_ptr)
-            _lib.call("hpri_cube_warp", _p(self._cubes), _DT[self.store_dtype], self.capacity, H, W, self.cs, self.C, ep,
-                      n, W, H, _p(self._out[k]), s)
-            _lib.call("hpri_mask_warp", _p(self._masks), self.capacity, H, W, ep, n, W, H, _p(self._mout[k]), s)
-        x = self._out[k][:n].view(n, W, H, self.cs)[:, :, :, :self.C].permute(0, 3, 1, 2)       # logical (N,C,W,H), channels-last strides
-        if self.unsqueeze:
-            x = x.unsqueeze(1)
-        x._hpri_zero_padded = True
-        x._hpri_slot = k
-        return {'image': x, 'mask': self._mout[k][:n].view(n, 1, W, H), 'index': [self._names[i] for i in slots]}
-
     def view(self, indices: Sequence[int], view: str) -> dict:
         """``{'image', 'mask', 'index'}`` of the WHOLE frame of the cached cubes ``indices`` in one of the eight dihedral views of
         ``hyperpri_amd.tta`` -- image and mask alike, bit for bit ``apply_view`` of ``batch(indices)``.  ``id``, ``flip_h``,
@@ -800,14 +796,13 @@ class CubeCache:
             raise ValueError("CubeCache.view: no indices")
         self._check_filled(idx)
         if code >= 4:
-            entries = view_warp_entries(idx, view, (self.H, self.W)).to(self.device)
-            out = self._warp_transposed(entries.data_ptr(), idx)
-            entries.record_stream(torch.cuda.current_stream(self.device))
-            return out
-        flags = {"id": 0, "flip_h": 1, "flip_w": 2, "rot180": 3}[view]
-        table = torch.tensor([[i, 0, 0, flags] for i in idx], dtype=torch.int32).to(self.device)
-        out = self._gather(table.data_ptr(), idx, self.H, self.W)
-        table.record_stream(torch.cuda.current_stream(self.device))
+            rows = view_warp_entries(idx, view, (self.H, self.W)).to(self.device)
+            out = self._launch(idx, (self.W, self.H), entries=rows.data_ptr(), transposed=True)
+        else:
+            flags = {"id": 0, "flip_h": 1, "flip_w": 2, "rot180": 3}[view]
+            rows = torch.tensor([[i, 0, 0, flags] for i in idx], dtype=torch.int32).to(self.device)
+            out = self._launch(idx, (self.H, self.W), table=rows.data_ptr())
+        rows.record_stream(torch.cuda.current_stream(self.device))
         return out
 
     def epoch_views(self, batch_size: int, views: Sequence[str]) -> Iterator[dict]:

@@ -11,9 +11,8 @@
 // The table lives on the device: {slot, top, left, flags} per sample, four int32 (flags bit 0: flip rows, bit 1: flip
 // columns).  The launchers cannot see it, so the kernels clamp slot / top / left into the cache: a bad table reads the wrong
 // window, never outside the allocation (hyperpri_amd/cache.py validates on the host before it uploads).
-#include "common.h"
+#include "cache_launch.h"
 
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 extern "C" int hpri_hwb_ingest(const void* src, int src_dtype, float* dst, long long P, int B, int lo, int C, int dst_cs,
@@ -128,25 +127,19 @@ __global__ __launch_bounds__(GATHER_THREADS) void cube_gather_kernel(const T* __
 // cache_dtype: 0 = float32, 1 = float16.  cache: (slots, Hs, Ws, cs); table: N entries of 4 int32 on the device; dst: (N, h, w, cs) fp32.
 extern "C" int hpri_cube_gather(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const int* table, int N,
                                 int h, int w, float* dst, hipStream_t stream) {
-  HPRI_REQUIRE(cache && table && dst, "cube_gather: null pointer");
-  HPRI_REQUIRE(cache_dtype == 0 || cache_dtype == 1, "cube_gather: cache_dtype must be 0 (f32) or 1 (f16)");
-  HPRI_REQUIRE(slots > 0 && Hs > 0 && Ws > 0 && N > 0, "cube_gather: bad sizes");
-  HPRI_REQUIRE(cs > 0 && cs % 8 == 0, "cube_gather: the channel stride must be a multiple of 8");
-  HPRI_REQUIRE(h > 0 && w > 0 && h <= Hs && w <= Ws, "cube_gather: the window does not fit the frame");
-  HPRI_REQUIRE((long long)w * (cs / 4) < 0x40000000LL && (long long)N * h < 0x7FFFFFFFLL, "cube_gather: window too large");
-  HPRI_REQUIRE(((uintptr_t)cache & 15) == 0 && ((uintptr_t)dst & 15) == 0 && ((uintptr_t)table & 15) == 0,
-               "cube_gather: buffers must be 16-byte aligned");
+  const CachePass p = {"cube_gather", slots, Hs, Ws, N, h, w, true};
+  CACHE_REQUIRE(p.who, cache && table && dst, "null pointer");
+  const CacheSlots c = {cache_dtype, cs, cs};
+  if (int e = cache_check(p, &c)) return e;
+  CACHE_REQUIRE(p.who, cache_aligned16(cache, dst, table), "buffers must be 16-byte aligned");
   const int q = cs / 4;
-  const long long pieces = ((long long)w * q + GATHER_ITEM - 1) / GATHER_ITEM;
-  long long blocks = (long long)N * h * pieces;
-  const long long cap = 8LL * hpri_cu_count();                      // eight workgroups per CU, grid-stride over the rest
-  if (blocks > cap) blocks = cap;
+  const dim3 grid = cache_grid(cache_row_items(p, q, GATHER_ITEM), 8);  // eight workgroups per CU, grid-stride over the rest
   if (cache_dtype == 0)
-    hipLaunchKernelGGL(cube_gather_kernel<float>, dim3((unsigned)blocks), dim3(GATHER_THREADS), 0, stream, (const float*)cache,
-                       slots, Hs, Ws, q, table, N, h, w, dst);
+    hipLaunchKernelGGL(cube_gather_kernel<float>, grid, dim3(GATHER_THREADS), 0, stream, (const float*)cache, slots, Hs, Ws, q, table, N,
+                       h, w, dst);
   else
-    hipLaunchKernelGGL(cube_gather_kernel<_Float16>, dim3((unsigned)blocks), dim3(GATHER_THREADS), 0, stream,
-                       (const _Float16*)cache, slots, Hs, Ws, q, table, N, h, w, dst);
+    hipLaunchKernelGGL(cube_gather_kernel<_Float16>, grid, dim3(GATHER_THREADS), 0, stream, (const _Float16*)cache, slots, Hs, Ws, q,
+                       table, N, h, w, dst);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;
 }
@@ -168,15 +161,12 @@ __global__ void mask_gather_kernel(const unsigned char* __restrict__ masks, int 
 // masks: uint8 (slots, Hs, Ws); dst: fp32 (N, 1, h, w); the table of hpri_cube_gather.
 extern "C" int hpri_mask_gather(const unsigned char* masks, int slots, int Hs, int Ws, const int* table, int N, int h, int w,
                                 float* dst, hipStream_t stream) {
-  HPRI_REQUIRE(masks && table && dst, "mask_gather: null pointer");
-  HPRI_REQUIRE(slots > 0 && Hs > 0 && Ws > 0 && N > 0, "mask_gather: bad sizes");
-  HPRI_REQUIRE(h > 0 && w > 0 && h <= Hs && w <= Ws, "mask_gather: the window does not fit the frame");
-  HPRI_REQUIRE((long long)N * h < 0x7FFFFFFFLL, "mask_gather: window too large");
-  HPRI_REQUIRE(((uintptr_t)table & 15) == 0, "mask_gather: the table must be 16-byte aligned");
-  long long blocks = ((long long)N * h * w + 255) / 256;
-  const long long cap = 8LL * hpri_cu_count();
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(mask_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, masks, slots, Hs, Ws, table, N, h, w, dst);
+  const CachePass p = {"mask_gather", slots, Hs, Ws, N, h, w, true};
+  CACHE_REQUIRE(p.who, masks && table && dst, "null pointer");
+  if (int e = cache_check(p)) return e;
+  CACHE_REQUIRE(p.who, cache_aligned16(table), "the table must be 16-byte aligned");
+  hipLaunchKernelGGL(mask_gather_kernel, cache_grid(cache_pixel_blocks(p), 8), dim3(256), 0, stream, masks, slots, Hs, Ws, table, N, h, w,
+                     dst);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;
 }

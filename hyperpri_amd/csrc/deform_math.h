@@ -1,4 +1,4 @@
-// The noise generator of the deforming gather (cache_deform.hip), shared by the device kernel and the host entry
+// The noise generator of the deforming gather (cache_warp.hip), shared by the device kernel and the host entry
 // hpri_deform_noise_host: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11; the Random123
 // constants) and the Box-Muller transform of its four output words.  Plain integer and fp32 arithmetic, no fast intrinsics: the
 // integer stream is the same on both sides bit for bit, the normals differ by the few ulps the two math libraries differ by.

@@ -579,7 +579,7 @@ int hpri_cube_warp(const void* cache, int cache_dtype, int slots, int Hs, int Ws
 int hpri_mask_warp(const unsigned char* masks, int slots, int Hs, int Ws, const int* entries, int N, int h, int w, float* dst,
                    hipStream_t stream);
 
-/* ---- cube cache, deforming gather (cache_deform.hip; hyperpri_amd/cache.py: CubeDeform) -------------------
+/* ---- cube cache, deforming gather (cache_warp.hip, cache_deform.hip; hyperpri_amd/cache.py: CubeDeform) ---
  * The warp pair's pass with an elastic displacement field in the coordinate, Gaussian noise in the value and a CutMix rectangle
  * that hands pixels to another sample of the batch.  Beside the warp entries a second record per sample:
  * Deform entry: 64 bytes = 16 32-bit words per sample, in DEVICE memory, 16-byte aligned:

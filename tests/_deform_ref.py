@@ -1,4 +1,4 @@
-"""fp64 / exact-integer restatement of the deforming gather (csrc/cache_deform.hip): the B-spline field, the CutMix owner of a pixel,
+"""fp64 / exact-integer restatement of the deforming gather (csrc/cache_warp.hip, csrc/cache_deform.hip): the B-spline field, the CutMix owner of a pixel,
 the displaced coordinates, Philox4x32-10 and Box-Muller.  Builds on the warp restatement of tests/test_cube_warp_cpu.py
 (``bilinear64`` / ``nearest64`` / ``entry_fields``); used by tests/test_cube_deform_cpu.py (which checks it against independent
 forms) and tests/test_gpu_cube_deform.py.  Also the case list the two files share."""

@@ -1,4 +1,4 @@
-"""Deforming gather of the cube cache (hyperpri_amd/cache.py: CubeDeform, plan_epoch_deformed; csrc/cache_deform.hip) -- CPU half:
+"""Deforming gather of the cube cache (hyperpri_amd/cache.py: CubeDeform, plan_epoch_deformed; csrc/cache_warp.hip, csrc/cache_deform.hip) -- CPU half:
 the C-ABI entry points exist and reject bad arguments without a launch, the noise generator is Philox4x32-10 bit for bit (through
 the library's host entry), its normals have the moments they should, the planner keeps ``plan_epoch_augmented``'s draws and makes
 its own in the documented order whatever the knobs are, the fp64 restatement (tests/_deform_ref.py) agrees with independent forms,

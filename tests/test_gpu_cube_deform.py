@@ -1,4 +1,4 @@
-"""Deforming gather of the cube cache on the device (csrc/cache_deform.hip through hyperpri_amd/cache.py): neutral entries give the
+"""Deforming gather of the cube cache on the device (csrc/cache_warp.hip, csrc/cache_deform.hip through hyperpri_amd/cache.py): neutral entries give the
 warp kernels' bits, the elastic field matches its fp64 restatement, deformed images lie within the warp test's tolerance and masks
 are exact, the noise is the documented Philox / Box-Muller stream, CutMix is a bit-exact ``torch.where`` of unmixed outputs, and
 epochs reproduce the host planner.  The restatement is tests/_deform_ref.py (checked by tests/test_cube_deform_cpu.py).

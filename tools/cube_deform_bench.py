@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Deforming gather of the cube cache (csrc/cache_deform.hip): what the elastic field, the noise and CutMix cost beside the warp kernel.
+"""Deforming gather of the cube cache (csrc/cache_warp.hip, csrc/cache_deform.hip): what the elastic field, the noise and CutMix cost beside the warp kernel.
 
     python tools/cube_deform_bench.py                  # one MI355X; writes profiles/cube_deform.json
     python tools/cube_deform_bench.py --out FILE --rounds 15 --calls 20
