@@ -5,8 +5,11 @@ Drop-in ``torch.nn.Module`` replacements for the reference's ``src/Experiments/m
 """
 from .cache import (CubeAugment, CubeCache, CubeDeform, deform_entries, elastic_lattice, plan_epoch, plan_epoch_augmented,  # noqa: F401
                     plan_epoch_deformed)
-from .evaluate import (SplitPrediction, color_classmaps, color_segmaps, default_class_palette, evaluate_multiclass,  # noqa: F401
-                       predict_split, test_net, tta_merge, validate_net, write_segmaps, write_spreadmaps)
+from .components import (TILE_H, TILE_W, clean_mask, clean_reference, component_table, components_reference,  # noqa: F401
+                         label_components)
+from .evaluate import (CLEAN_LOGIT, SplitPrediction, clean_prediction, color_classmaps, color_segmaps, default_class_palette,  # noqa: F401
+                       evaluate_multiclass, object_metrics, predict_split, test_net, tta_merge, validate_net, write_segmaps,
+                       write_spreadmaps)
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)

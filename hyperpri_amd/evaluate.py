@@ -20,6 +20,13 @@ network sees every view of a batch, ``CubeCache.epoch_views`` makes the views wi
     pred = predict_split(net, cache.epoch_views(2, tta.views), tta=tta)      # pred.logits: the logit of the mean probability
     val  = validate_net(pred); write_spreadmaps(fig_dir, pred)
 
+Objects instead of pixels (``hyperpri_amd.components``, ``csrc/components.hip``) are opt-in as well: ``clean_prediction`` drops the
+specks and closes the pinholes of a stored split at the chosen threshold and hands back a prediction that ``test_net`` and
+``write_segmaps`` take unchanged; ``object_metrics`` counts and measures predicted and true components:
+
+    cleaned, stats = clean_prediction(pred, val["best_threshold"], min_area=8, max_hole=4)
+    test = test_net(cleaned, val["best_threshold"]); objs = object_metrics(pred, val["best_threshold"], min_area=8)
+
 Lightning-free and torchmetrics-free like ``trainer.py``, whose device pieces this module composes (``hpri_bce_logits_fwd``,
 ``SegCounts``, ``PRCurve``, ``best_dice_threshold``, ``average_precision``); the maps are one kernel of their own
 (``csrc/segmap.hip``).  There is no CPU fallback: tensors must be fp32 on a ROCm device.
@@ -578,4 +585,100 @@ def evaluate_multiclass(network: nn.Module, batches: Iterable[dict], num_classes
         out["paths"] = paths
         if tta is not None and tta.spread:
             out["spread_paths"] = spread_paths
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Objects (csrc/components.hip, hyperpri_amd/components.py): clean a stored prediction, count and measure what it found
+# ---------------------------------------------------------------------------------------------------
+CLEAN_LOGIT = 16.0      # fp32 sigmoid(+-16) = 1 - 1.2e-7 and 1.1e-7: strictly inside (0, 1) and on either side of any threshold in [1e-6, 1 - 1e-6]
+
+
+def _size_groups(pred: SplitPrediction) -> List[Tuple[int, int]]:
+    """Runs [i, j) of consecutive images of one size, none holding 2^31 pixels or more."""
+    groups, i = [], 0
+    while i < len(pred):
+        h, w = pred.sizes[i]
+        limit = max(1, (2 ** 31 - 1) // (h * w))
+        j = i + 1
+        while j < len(pred) and pred.sizes[j] == (h, w) and j - i < limit:
+            j += 1
+        groups.append((i, j))
+        i = j
+    return groups
+
+
+def clean_prediction(pred: SplitPrediction, threshold: float, min_area: int = 0, max_hole: int = 0,
+                     connectivity: int = 8) -> Tuple[SplitPrediction, Dict[str, int]]:
+    """Drop the specks and close the pinholes of a stored split on the device (``components.clean_mask``'s kernels): the decision
+    ``sigmoid(logits) > threshold`` of every image loses its foreground components (``connectivity``) of fewer than ``min_area``
+    pixels and gains its background components (the dual connectivity) of at most ``max_hole`` pixels that touch no image edge.
+    Consecutive images of equal size are cleaned in one launch sequence.  Returns ``(cleaned, stats)``:
+
+    * ``cleaned``: a ``SplitPrediction`` with the same masks, offsets, sizes, names (and spread) whose ``logits`` are
+      ``+CLEAN_LOGIT`` where the cleaned decision is foreground and ``-CLEAN_LOGIT`` elsewhere.  fp32 sigmoid(+-16) lies strictly
+      inside (0, 1), so ``test_net(cleaned, thr)``, ``write_segmaps(dir, cleaned, batches, thr)`` and ``SegCounts`` reproduce the
+      cleaned decision for ANY threshold in [1e-6, 1 - 1e-6], unchanged.  With ``min_area=0, max_hole=0`` the decisions are those
+      of ``pred`` at ``threshold``.
+    * ``stats``: ``components_removed``, ``pixels_removed``, ``holes_filled``, ``pixels_filled`` over the split (reading them is
+      the one host synchronisation).
+
+    A cleaned prediction holds two logit values, so its ``avg_prec`` and its PR curve (``validate_net``) are degenerate: ranking
+    metrics and the threshold search belong to the raw prediction; clean at the threshold they picked."""
+    from . import components as C
+    _require_cuda(pred.logits, "prediction to clean")
+    min_area, max_hole, connectivity = C._check_clean_args(min_area, max_hole, connectivity)
+    with torch.cuda.device(pred.logits.device):
+        src = pred.logits.detach().contiguous()
+        out = torch.empty_like(src)
+        stats = torch.zeros(4, dtype=torch.int64, device=src.device)
+        for i, j in _size_groups(pred):
+            a, b, (h, w) = pred.offsets[i], pred.offsets[j], pred.sizes[i]
+            C._clean_launch(src[a:b].view(j - i, h, w), 0, float(threshold), True, min_area, max_hole, connectivity, stats,
+                            logits_out=out[a:b], logit=CLEAN_LOGIT)
+        cleaned = SplitPrediction(out, pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
+        return cleaned, C.stats_dict(stats)
+
+
+def object_metrics(pred: SplitPrediction, threshold: float, connectivity: int = 8, min_area: int = 0) -> Dict[str, object]:
+    """Count and measure the objects of a stored split: the components of ``sigmoid(logits) > threshold`` (after
+    ``clean_prediction(pred, threshold, min_area)`` when ``min_area > 0``) and those of the masks (``int(mask) != 0``), labelled the
+    same way.  Returns
+
+    * ``pred_objects``, ``pred_objects_hit`` (predicted components with at least one true pixel);
+    * ``truth_objects``, ``truth_objects_hit`` (true components with at least one predicted pixel);
+    * ``object_precision`` = hit / predicted, ``object_recall`` = hit / true, ``object_f1`` = 2PR / (P + R) (NaN on a zero
+      denominator, as the pixel metrics);
+    * ``pred_areas``, ``truth_areas``: per image the areas of its components in label order.
+
+    Labelling and measuring run on the device; one small table per group of equal-sized images comes to the host."""
+    from . import components as C
+    _require_cuda(pred.logits, "prediction to measure")
+    _require_device(pred.masks, "evaluation mask")
+    connectivity = C._check_connectivity(connectivity)
+    if int(min_area) > 0:
+        pred, threshold = clean_prediction(pred, threshold, min_area, 0, connectivity)[0], 0.5
+    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
+    tot = {"pred_objects": 0, "pred_objects_hit": 0, "truth_objects": 0, "truth_objects_hit": 0}
+    pred_areas: List[List[int]] = []
+    truth_areas: List[List[int]] = []
+    for i, j in _size_groups(pred):
+        a, b, (h, w) = pred.offsets[i], pred.offsets[j], pred.sizes[i]
+        x, m = pred.logits[a:b].view(j - i, h, w), masks[a:b].view(j - i, h, w)
+        lp, cp = C.label_components(x, float(threshold), True, connectivity)
+        lt, ct = C._label_truth(m, connectivity)
+        tp, tt = C.component_table(lp, cp, truth=m), C.component_table(lt, ct, truth=lp)
+        tot["pred_objects"] += len(tp["area"])
+        tot["pred_objects_hit"] += int((tp["overlap"] > 0).sum())
+        tot["truth_objects"] += len(tt["area"])
+        tot["truth_objects_hit"] += int((tt["overlap"] > 0).sum())
+        for n in range(j - i):
+            pred_areas.append([int(v) for v in tp["area"][tp["image"] == n]])
+            truth_areas.append([int(v) for v in tt["area"][tt["image"] == n]])
+    nan = float("nan")
+    p = tot["pred_objects_hit"] / tot["pred_objects"] if tot["pred_objects"] else nan
+    r = tot["truth_objects_hit"] / tot["truth_objects"] if tot["truth_objects"] else nan
+    out: Dict[str, object] = dict(tot)
+    out.update(object_precision=p, object_recall=r, object_f1=2 * p * r / (p + r) if p + r > 0 else nan,
+               pred_areas=pred_areas, truth_areas=truth_areas)
     return out

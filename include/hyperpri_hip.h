@@ -747,6 +747,46 @@ int hpri_seg_loss_bwd(const float* logits, const float* target, int n_img, long 
 int hpri_tta_merge(const float* const* views, const int* codes, int V, int N, int K, int h, int w, int mode, float* out,
                    float* spread, hipStream_t stream);
 
+/* ---- connected components (components.hip; hyperpri_amd/components.py, evaluate.py) ------------------------
+ * Label a binary decision map, measure its components, clean it; all results are integers.
+ *   pred        contiguous (N, h, w), N*h*w < 2^31; pred_kind 0 = fp32, decided as hpri_seg_counts / hpri_segmap_overlay decide:
+ *               p = is_logits ? 1 / (1 + expf(-x)) : x;  fg = p > threshold;   pred_kind 1 = uint8, fg = value != 0;
+ *               pred_kind 2 = fp32 mask, fg = ((int)value) != 0, how the tail reads a mask (1, 2: threshold and is_logits unused).
+ *               invert != 0 labels the background instead.
+ *   connectivity  4 or 8.  Images never connect to each other.
+ *   workspace   hpri_cc_workspace_ints 32-bit words on the device (pure host function; 0 for a bad shape), contents scratch.
+ * Labelling is union-find over linear indices with parent[i] <= i (background -1; the root of a component is its smallest index):
+ * a per-tile pass in LDS (hpri_cc_tile_h x hpri_cc_tile_w pixels per workgroup), a border pass that unites neighbours across tile
+ * edges in global memory (every access to parent an agent-scope atomic: relaxed load / atomicMin), an out-of-place flatten.  The
+ * phases are separate launches on `stream`; no workgroup waits for another; every loop over parent ends because an index (find) or a
+ * value (union by atomicMin, retried on the returned value) strictly decreases.  Integer atomics only: bit-reproducible.
+ *   hpri_cc_label    labels (N, h, w) int32: 0 background, 1..counts[n] per image in raster order of each component's first pixel
+ *                    (the rank of its root; the numbering of scipy.ndimage.label);  counts (N) int32.
+ *   hpri_cc_measure  one pass over labels: table row offsets[n] + label - 1 (rows ordered by image, label) = six int32: area, y0,
+ *                    x0, y1, x1 (inclusive box), overlap = pixels of the component where ((int)truth) != 0 (0 without truth; truth
+ *                    contiguous (N, h, w), truth_kind 0 = fp32, 1 = uint8, 2 = int32: value != 0, e.g. another label map).
+ *                    table_rows >= sum of counts: rows past table_rows are never written; offsets: N + 1 int32 of device
+ *                    scratch.  table_rows = 0: nothing is launched.
+ *   hpri_cc_clean    out (N, h, w) uint8 = the cleaned decision: a foreground component (connectivity) with area < min_area becomes
+ *                    background; a background component -- labelled with the DUAL connectivity, 4 for foreground 8 and 8 for
+ *                    foreground 4 -- whose box touches no image edge and whose area <= max_hole becomes foreground.  Holes are
+ *                    found in the input decision, not after speck removal: the two edits act on disjoint pixels, so their order
+ *                    is immaterial.  out_logits (nullable): (N, h, w) fp32, +logit where the cleaned decision is foreground
+ *                    and -logit elsewhere.  stats: four int64 on the device, ACCUMULATED like the buffer of hpri_seg_counts:
+ *                    components removed, pixels removed, holes filled, pixels filled.
+ * Argument errors (a null pointer, N, h or w <= 0, N*h*w >= 2^31, connectivity not 4 or 8, a kind outside 0..2, min_area or max_hole
+ * negative) return -1 before any launch; a workspace that is too small returns -3. */
+size_t hpri_cc_workspace_ints(int N, int h, int w);
+int hpri_cc_tile_h(void);
+int hpri_cc_tile_w(void);
+int hpri_cc_label(const void* pred, int pred_kind, float threshold, int is_logits, int invert, int N, int h, int w,
+                  int connectivity, int* labels, int* counts, int* workspace, size_t ws_ints, hipStream_t stream);
+int hpri_cc_measure(const int* labels, const int* counts, const void* truth, int truth_kind, int N, int h, int w, int* table,
+                    int table_rows, int* offsets, hipStream_t stream);
+int hpri_cc_clean(const void* pred, int pred_kind, float threshold, int is_logits, int N, int h, int w, int connectivity,
+                  int min_area, int max_hole, unsigned char* out, float* out_logits, float logit, long long* stats,
+                  int* workspace, size_t ws_ints, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
