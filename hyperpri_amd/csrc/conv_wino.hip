@@ -11,6 +11,8 @@
 // results differ from the direct sum by fp32 rounding of the transforms only (measured: profiles/r02_precision_error.json).
 #include "common.h"
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
 // Floats of a packed transformed filter U: 16 frequencies x (K rounded up to 8) x Ncols_pad (layout: hpri_wino4_pack, conv_wino4.hip).
 extern "C" size_t hpri_wino_packed_floats(int K, int Ncols_pad) { return (size_t)hpri_cdiv(K, 8) * 16 * 8 * Ncols_pad; }
 
@@ -25,8 +27,8 @@ extern "C" size_t hpri_wino_packed_floats(int K, int Ncols_pad) { return (size_t
 //              writes ONE partial slab ws[split][xi][cin][cout]; hpri_wino_wgrad_reduce sums the slabs in a fixed order
 //              (deterministic) and applies G^T . G on the way into the OIHW gradient.
 //   stage      one strip of 16 tiles (2 output rows x 32 columns): input halo 4 x 34 pixels x 64 cin and dY 2 x 32 pixels
-//              x 64 cout, both [pixel][channel] by LDS-DMA (lanes index the channel: every ds_read_b32 is 32 consecutive
-//              dwords), double buffered; 64 MFMAs per wave, one barrier.
+//              x 64 cout, both [pixel][channel] by LDS-DMA (lanes index the channel PAIR: every ds_read_b64 is a pixel's 256
+//              consecutive bytes), double buffered; 64 MFMAs per wave, one barrier.
 //   edge       the last strip of a strip row hangs over the right image edge; its dY beyond W is zero-filled, so dM = A 0 A^T = 0
 //              there.  MFMA k-step kk multiplies the pixel columns x0 + 4 kk .. + 3: a strip runs kend = min(8, ceil((W - x0) / 4))
 //              k-steps (wave-uniform; a k-step is left out only when ALL four of its columns are >= W).  Accumulators start at
@@ -65,11 +67,9 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
   const int c_blk = cb * 64, n_blk = nbk * 64;
   const int u0 = split * a.per_split, u1 = min(a.total, u0 + a.per_split);
 
-  // input-transform roles (as the forward kernel): rows r1, r2 with signs, columns c0 .. c0+2
-  const int r1 = (fa == 0) ? 0 : 1, r2 = (fa == 3) ? 3 : 2;
-  const float s1 = (fa == 2) ? -1.f : 1.f, s2 = (fa == 1 || fa == 2) ? 1.f : -1.f;
-  const int c0 = fb;
-  const float sigma = s1 * s2;
+  // input-transform roles (as the forward kernel): V row fa = s1 (d[r1] + s1 s2 d[r2]) with r1 = 0 1 1 1, r2 = 2 2 2 3, s1 = + + - +,
+  // s2 = - + + -, columns fb .. fb + 2.  Rows and s1 s2 are compile-time in K_STEP; s1 is applied when the slab is written.
+  const float s1 = (fa == 2) ? -1.f : 1.f;
 
   f32x16 acc[2][2][2];                              // [frequency e][cin tile ct][cout tile nt]
 #pragma unroll
@@ -92,11 +92,13 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
   const int l4 = lane >> 4;                          // pixel of the piece's group of four
   const unsigned xlane = (c_blk + (lane & 15) * 4 < a.x_cvalid) ? (unsigned)(l4 * a.x_cs * 4 + (lane & 15) * 16) : OOB;
   const unsigned ylane = (n_blk + (lane & 15) * 4 < a.dy_cvalid) ? (unsigned)(l4 * a.dy_cs * 4 + (lane & 15) * 16) : OOB;
-#define LOAD_UNIT(u_, buf_)                                                                                            \
+  // units are loaded in order, u0, u0 + 1, ...: the (strip column, strip row, image) of the next one is carried along and
+  // wrapped, not divided out of the unit index every time
+  int ld_sx = u0 % a.strips_x, ld_sy = (u0 / a.strips_x) % a.strips_y, ld_img = u0 / (a.strips_x * a.strips_y);
+#define LOAD_UNIT(buf_)                                                                                                \
   {                                                                                                                    \
-    int q_ = (u_);                                                                                                     \
-    const int sx_ = q_ % a.strips_x; q_ /= a.strips_x;                                                                 \
-    const int sy_ = q_ % a.strips_y; const int img_ = q_ / a.strips_y;                                                 \
+    const int sx_ = ld_sx, sy_ = ld_sy, img_ = ld_img;                                                                 \
+    if (++ld_sx == a.strips_x) { ld_sx = 0; if (++ld_sy == a.strips_y) { ld_sy = 0; ++ld_img; } }                      \
     const int y0_ = sy_ * 2, x0_ = sx_ * 32;                                                                           \
     kend_next = min(8, (a.kw - x0_ + 3) >> 2);                /* k-steps of this unit (wave-uniform) */                \
     unsigned char* lb_ = smem + (buf_) * WG_STAGE_BYTES;                                                               \
@@ -124,44 +126,74 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 // 0 or +-1 -- a = 0: dY[0], a = 1: dY[0] + dY[1], a = 2: dY[0] - dY[1], a = 3: -dY[1] -- so rows 0 and 3 need no arithmetic at
 // all and rows 1, 2 one add per column; the column part for b = 2 fb + e is t0 | t0 + t1 (fb = 0), t0 - t1 | -t1 (fb = 1).  The
 // two minus signs (row 3, and b = 3) are left out here and applied once to the accumulators when the slab is written.
-// ONE loop with the unit's trip count kend (odd at W = 121 and W = 60: exact, no remainder step).  hipcc does not unroll it
-// (`unroll 2` with the constant trip count 8 gave 16 MFMAs, 40-61 vector and 16-20 LDS instructions per two k-steps; this gives 8,
-// 19-29 and 8-10 per k-step, 185 registers either way).  A second copy of the loop for short strips (constant-trip loop for
-// kend = 8, runtime loop otherwise) inside the unit loop spills 2044 registers, with or without an opaque lane id: rejected.
-// Two k-steps per trip plus a straight-line odd step keeps the unrolled schedule (the second k-step's reads among the first one's
-// MFMAs) at 4-5 more vector instructions per pair, and measured no faster than running all 8 (experiments/README.md).
+// ONE loop with the unit's trip count kend (odd at W = 121 and W = 60: exact, no remainder step), not unrolled.  A second copy of
+// the loop for short strips (constant-trip loop for kend = 8, runtime loop otherwise) inside the unit loop spills 2044 registers,
+// with or without an opaque lane id: rejected.  Two k-steps per trip plus a straight-line odd step measured no faster than
+// running all 8 (experiments/README.md).
+// Every vector or LDS instruction of the k-step is paid in matrix-pipe time, so the step holds the transform and
+// nothing else: 13 (rows 0, 3) or 17 (rows 1, 2) vector and 8 or 10 LDS instructions per 8 MFMAs, 159 registers
+// (profiles/wgrad_kstep_isa_census.json; before: 19-29 and 8-10, 185).
+//   operands   lane li holds input channels 2 li, 2 li + 1 (its cin tiles ct = 0, 1) and output channels 2 li, 2 li + 1 (its cout
+//              tiles nt = 0, 1): both tiles' operands of a pixel are ONE ds_read_b64 (conflict-free: 32 lanes x 8 bytes are the
+//              pixel's 256 bytes).  Which channel sits in which MFMA row or column changes no sum; the slab write puts them back.
+//   address    ONE register, kp = stage + lh * 512 + li * 8, + 1024 per k-step; rows, columns and the dY block are immediates
+//              (the stage is 52 KB, a ds_read offset reaches 64 KB).  The reads are volatile so that hipcc leaves them single:
+//              merged into ds_read2_b64 pairs each pair got a base register of its own and an add per k-step (3-6 adds).
+//   transform  scalar adds and subtracts; WG_PIN (an empty asm on the value) keeps hipcc's SLP vectoriser from pairing them into
+//              v_pk_add_f32 / v_pk_fma_f32, which cost more per flop and took 6-12 v_mov_b32 to pack their operands.  The row
+//              signs s1 s2 are compile-time per variant: d1 + s1 s2 d2 is one add or one subtract, the same bits as the FMA.
+//   schedule   sched_barrier: operands first, then the 8 MFMAs back to back (left alone hipcc spread the transform between the
+//              MFMAs and re-used operand registers: 7-8 s_nop per k-step).
 #define K_STEP(FA_, FB_)                                      /* MFMA k-step kk: tiles 2 kk + lh of the strip */         \
     {                                                                                                                  \
-      const int tile = 2 * kk + lh;                                                                                    \
+      constexpr int R1_ = (FA_ == 0) ? 0 : 1, R2_ = (FA_ == 3) ? 3 : 2;             /* halo rows of the row transform */ \
+      constexpr int YR_ = (FA_ == 3) ? 1 : 0, YROWS_ = (FA_ == 1 || FA_ == 2) ? 2 : 1;                                 \
+      asm("" : "+v"(kp));                           /* the ONE address register; everything else is an immediate */    \
+      f32x2 d[2][3], y[2][2];                       /* x [row r1 | r2][column c], dY [row][pixel] */                   \
+      _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                                                  \
+        d[0][c] = WG_LDS2(kp + (R1_ * WG_XROW + FB_ + c) * 256);                                                       \
+        d[1][c] = WG_LDS2(kp + (R2_ * WG_XROW + FB_ + c) * 256);                                                       \
+      }                                                                                                                \
+      _Pragma("unroll") for (int r = 0; r < YROWS_; ++r)                                                               \
+        _Pragma("unroll") for (int px = 0; px < 2; ++px) y[r][px] = WG_LDS2(kp + WG_X_BYTES + ((YR_ + r) * 32 + px) * 256); \
       float va[2][2], vb[2][2];                     /* [frequency e][cin tile | cout tile] */                          \
+      float P[3][2];                                                                                                   \
+      _Pragma("unroll") for (int c = 0; c < 3; ++c)                                                                    \
+        _Pragma("unroll") for (int ct = 0; ct < 2; ++ct) {                                                             \
+          float d1_ = d[0][c][ct], d2_ = d[1][c][ct];                                                                  \
+          WG_PIN(d1_) WG_PIN(d2_)                                                                                      \
+          P[c][ct] = (FA_ == 1) ? (d1_ + d2_) : (d1_ - d2_);            /* d1 + s1 s2 d2 */                            \
+          WG_PIN(P[c][ct])                                                                                             \
+        }                                                                                                              \
       _Pragma("unroll") for (int ct = 0; ct < 2; ++ct) {                                                               \
-        float P[3];                                                                                                    \
-        _Pragma("unroll") for (int c = 0; c < 3; ++c) {                                                                \
-          const float d1 = xs[(r1 * WG_XROW + 2 * tile + c0 + c) * 64 + ct * 32 + li];                                 \
-          const float d2 = xs[(r2 * WG_XROW + 2 * tile + c0 + c) * 64 + ct * 32 + li];                                 \
-          P[c] = d1 + sigma * d2;                                                                                      \
-        }                                                                                                              \
-        va[0][ct] = FB_ ? (P[1] - P[0]) : (P[0] - P[2]);                                                               \
-        va[1][ct] = FB_ ? (P[0] - P[2]) : (P[1] + P[2]);                                                               \
+        va[0][ct] = FB_ ? (P[1][ct] - P[0][ct]) : (P[0][ct] - P[2][ct]);                                               \
+        va[1][ct] = FB_ ? (P[0][ct] - P[2][ct]) : (P[1][ct] + P[2][ct]);                                               \
+                                                                                                                       \
       }                                                                                                                \
+      float t[2][2];                                /* [pixel of the tile][cout tile] */                               \
+      _Pragma("unroll") for (int px = 0; px < 2; ++px)                                                                 \
+        _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) {                                                             \
+          float y0_ = y[0][px][nt];                                                                                    \
+          WG_PIN(y0_)                                                                                                  \
+          if (YROWS_ == 2) {                                                                                           \
+            float y1_ = y[1][px][nt];                                                                                  \
+            WG_PIN(y1_)                                                                                                \
+            y0_ = (FA_ == 1) ? (y0_ + y1_) : (y0_ - y1_);                                                              \
+            WG_PIN(y0_)                                                                                                \
+          }                                                                                                            \
+          t[px][nt] = y0_;                                                                                             \
+        }                                                                                                              \
       _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) {                                                               \
-        float t0, t1;                                                                                                  \
-        if (FA_ == 0 || FA_ == 3) {                                                                                    \
-          t0 = ys[(((FA_ == 3) ? 1 : 0) * 32 + 2 * tile + 0) * 64 + nt * 32 + li];                                     \
-          t1 = ys[(((FA_ == 3) ? 1 : 0) * 32 + 2 * tile + 1) * 64 + nt * 32 + li];                                     \
-        } else {                                                                                                       \
-          const float y00 = ys[(0 * 32 + 2 * tile + 0) * 64 + nt * 32 + li], y01 = ys[(0 * 32 + 2 * tile + 1) * 64 + nt * 32 + li]; \
-          const float y10 = ys[(1 * 32 + 2 * tile + 0) * 64 + nt * 32 + li], y11 = ys[(1 * 32 + 2 * tile + 1) * 64 + nt * 32 + li]; \
-          t0 = (FA_ == 1) ? (y00 + y10) : (y00 - y10);                                                                 \
-          t1 = (FA_ == 1) ? (y01 + y11) : (y01 - y11);                                                                 \
-        }                                                                                                              \
-        vb[0][nt] = FB_ ? (t0 - t1) : t0;                                                                              \
-        vb[1][nt] = FB_ ? t1 : (t0 + t1);                                                                              \
+        vb[0][nt] = FB_ ? (t[0][nt] - t[1][nt]) : t[0][nt];                                                            \
+        vb[1][nt] = FB_ ? t[1][nt] : (t[0][nt] + t[1][nt]);                                                            \
+                                                                                                                       \
       }                                                                                                                \
+      __builtin_amdgcn_sched_barrier(0);            /* operands first, then the 8 MFMAs back to back */                \
       _Pragma("unroll") for (int e = 0; e < 2; ++e)                                                                    \
           _Pragma("unroll") for (int ct = 0; ct < 2; ++ct)                                                             \
               _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                         \
                   acc[e][ct][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[e][ct], vb[e][nt], acc[e][ct][nt], 0, 0, 0); \
+      kp += 1024;                                   /* four pixel columns on */                                        \
     }
   // the variant is chosen once per wave, outside the unit loop (eight copies of the loop, no selects inside)
 #define UNIT_LOOP(FA_, FB_)                                                                                            \
@@ -169,13 +201,18 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                   \
     __builtin_amdgcn_s_barrier();          /* this unit has landed for everyone; the other buffer is free */           \
     const int kend = kend_next;                                                                                        \
-    if (u + 1 < u1) LOAD_UNIT(u + 1, (u + 1 - u0) & 1)                                                                 \
-    const float* xs = reinterpret_cast<const float*>(smem + ((u - u0) & 1) * WG_STAGE_BYTES);                          \
-    const float* ys = xs + WG_X_BYTES / 4;                                                                             \
-    _Pragma("unroll 2") for (int kk = 0; kk < kend; ++kk) K_STEP(FA_, FB_)                                             \
+    if (u + 1 < u1) LOAD_UNIT((u + 1 - u0) & 1)                                                                         \
+    unsigned kp = ((u - u0) & 1) * WG_STAGE_BYTES + klane;                                                             \
+    for (int kk = 0; kk < kend; ++kk) K_STEP(FA_, FB_)                                                                 \
   }
+  const unsigned klane = (unsigned)(lh * 512 + li * 8);
+  typedef __attribute__((address_space(3))) const unsigned char* wg_lds_bytes;
+  typedef __attribute__((address_space(3))) const volatile f32x2* wg_lds_f32x2;
+  const wg_lds_bytes lds = (wg_lds_bytes)smem;
+#define WG_LDS2(off_) (*(wg_lds_f32x2)(lds + (off_)))
+#define WG_PIN(v_) asm("" : "+v"(v_));
   int kend_next = 8;
-  if (u0 < u1) LOAD_UNIT(u0, 0)
+  if (u0 < u1) LOAD_UNIT(0)
   switch (wave) {                          // wave = 2 fa + fb
     case 0: UNIT_LOOP(0, 0) break;
     case 1: UNIT_LOOP(0, 1) break;
@@ -189,6 +226,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 #undef UNIT_LOOP
 #undef K_STEP
 #undef LOAD_UNIT
+#undef WG_LDS2
+#undef WG_PIN
   // slab: ws[split][xi][c][n]; accumulator rows = cin (register index), columns = cout (lane)
   float* slab = a.ws + (size_t)split * 16 * a.Cr * a.Nr;
   const float sdy = (fa == 3) ? -s1 : s1;                              // input-transform row sign x dY row sign
@@ -199,13 +238,12 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int n = n_blk + nt * 32 + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int c = c_blk + ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          slab[((size_t)xi * a.Cr + c) * a.Nr + n] = sgn[e] * acc[e][ct][nt][r];   // the transform signs left out of the loop
-        }
+      for (int r = 0; r < 16; ++r) {
+        const int c = c_blk + 2 * ((r & 3) + 8 * (r >> 2) + 4 * lh) + ct;
+        f32x2 o;                                                            // cout 2 li (nt = 0) and 2 li + 1 (nt = 1)
+        o[0] = sgn[e] * acc[e][ct][0][r];                                   // the transform signs left out of the loop
+        o[1] = sgn[e] * acc[e][ct][1][r];
+        *reinterpret_cast<f32x2*>(&slab[((size_t)xi * a.Cr + c) * a.Nr + n_blk + 2 * li]) = o;
       }
   }
 }

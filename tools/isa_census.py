@@ -3,7 +3,13 @@
 MFMA of conv_bf16v3 come from?): the kernel's gfx950 assembly (hipcc -S) split at its first and last v_mfma -- "before" (set-up),
 "loop" (the k loop: everything between the first and the last MFMA) and "after" (epilogue + next item's set-up) -- with each
 region's instructions by class.  A static count weights every instruction once; the k loop's body runs Cin_pad / 64 times per item
-and the rest once, which the "per_item" estimate applies.   usage: isa_census.py conv_bf16v3.hip conv_bf16v3_kernel [chunks_per_item]"""
+and the rest once, which the "per_item" estimate applies.   usage: isa_census.py conv_bf16v3.hip conv_bf16v3_kernel [chunks_per_item]
+
+Second form, for a kernel with several k loops (conv_wino_wgrad_kernel: one per wave variant):
+    isa_census.py --loops conv_wino.hip conv_wino_wgrad_kernel [mfmas_per_k_step] [--source FILE]
+lists every innermost single-block loop that holds an MFMA, in the order of the listing: MFMAs, vector instructions by mnemonic,
+LDS instructions by mnemonic, waits, per k-step (the loop's MFMAs / mfmas_per_k_step, default 8), what the loop around it holds
+outside the k loop (the per-unit bookkeeping, counted statically), and the kernel's registers and scratch.  --source compiles another copy of the file (the parent's, say) with csrc/ as the include directory."""
 import json
 import os
 import re
@@ -12,6 +18,89 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def loops_census(argv):
+    """Every innermost MFMA loop of one kernel: a label, no other label, and a conditional branch back to it."""
+    source = None
+    if "--source" in argv:
+        i = argv.index("--source")
+        source = argv[i + 1]
+        argv = argv[:i] + argv[i + 2:]
+    src, kern = argv[0], argv[1]
+    per_step = int(argv[2]) if len(argv) > 2 else 8
+    csrc = os.path.join(ROOT, "hyperpri_amd", "csrc")
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-S", "--cuda-device-only",
+                               "-I", csrc, source or os.path.join(csrc, src), "-o", out], stderr=subprocess.DEVNULL)
+        text = open(out).read()
+    m = re.search(r"^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\s*s_endpgm" % re.escape(kern), text, re.S | re.M)
+    name, body = m.group(1), m.group(2)
+
+    def meta(key):
+        mm = re.search(r"\.set %s\.%s, (\d+)" % (re.escape(name), key), text)
+        return int(mm.group(1)) if mm else None
+
+    # hipcc marks every block of a loop in the comment of its label ("in Loop: Header=BB0_43 Depth=1"; the inner loop's own
+    # header: "Parent Loop BB0_43 Depth=1"): `outer` collects what a depth-1 loop holds outside its inner loops, i.e. the
+    # per-unit bookkeeping around a k loop
+    loops, label, block, where, outer, parent = [], None, [], None, {}, {}
+    for ln in body.splitlines():
+        lab = re.match(r"^(\.LBB\d+_\d+):(.*)", ln) or re.match(r"^; (%bb\.\d+):(.*)", ln)
+        if lab:
+            if lab.group(1).startswith("."):
+                label, block = lab.group(1), []
+            note = lab.group(2)
+            hdr = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=1", note)
+            par = re.search(r"Parent Loop (BB\d+_\d+) Depth=1", note)
+            if "This Loop Header: Depth=1" in note:
+                where = lab.group(1)[2:]
+            elif hdr:
+                where = hdr.group(1)
+            elif par:
+                where, parent[lab.group(1)] = None, par.group(1)
+            else:
+                where = None
+            continue
+        if not ln.startswith("\t") or ln.strip().startswith((";", ".")):
+            continue
+        tok = ln.split(";")[0].split()
+        block.append(tok[0])
+        if where:
+            outer.setdefault(where, []).append(tok[0])
+        if tok[0].startswith("s_cbranch") and tok[1] == label and any(x.startswith("v_mfma") for x in block):
+            loops.append((label, block))
+
+    def by_mnemonic(xs):
+        c = {}
+        for x in xs:
+            x = re.sub(r"_e32$|_e64$", "", x)
+            c[x] = c.get(x, 0) + 1
+        return dict(sorted(c.items()))
+
+    rows = []
+    for label, block in loops:
+        mfma = sum(x.startswith("v_mfma") for x in block)
+        steps = mfma / per_step
+        valu = [x for x in block if x.startswith("v_") and not x.startswith("v_mfma")]
+        lds = [x for x in block if x.startswith("ds_")]
+        rows.append({"loop": label, "mfma": mfma, "k_steps_per_trip": steps,
+                     "vector_per_k_step": round(len(valu) / steps, 2), "lds_per_k_step": round(len(lds) / steps, 2),
+                     "vector": by_mnemonic(valu), "lds": by_mnemonic(lds),
+                     "s_nop": sum(x == "s_nop" for x in block), "s_waitcnt": sum(x == "s_waitcnt" for x in block),
+                     "packed_f32": sum(bool(re.match(r"v_pk_\w+_f32", x)) for x in block)})
+        unit = outer.get(parent.get(label), [])
+        rows[-1]["per_unit_outside_the_k_loop (static: both sides of every branch)"] = {
+            "vector": sum(x.startswith("v_") for x in unit), "scalar": sum(x.startswith("s_") and not x.startswith(("s_waitcnt", "s_nop")) for x in unit),
+            "vector_memory": sum(x.startswith(("buffer_", "global_")) for x in unit)}
+    print(json.dumps({"kernel": name, "source": source or src, "vgprs": meta("num_vgpr"), "agprs": meta("num_agpr"),
+                      "scratch_bytes": meta("private_seg_size"), "mfma_loops": rows}, indent=1))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--loops":
+    loops_census(sys.argv[2:])
+    sys.exit(0)
 src, kern = sys.argv[1], sys.argv[2]
 chunks = int(sys.argv[3]) if len(sys.argv) > 3 else 8
 csrc = os.path.join(ROOT, "hyperpri_amd", "csrc")
