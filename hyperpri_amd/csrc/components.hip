@@ -38,7 +38,7 @@
 // (its bounding box does not reach row 0, row h-1, column 0 or column w-1 -- equivalently none of its pixels lies there) and has
 // area <= max_hole becomes foreground.  Holes are found in the INPUT decision, not after speck removal: the two edits act on
 // disjoint pixels (one on foreground, one on background pixels of the input), so their order is immaterial.
-#include "common.h"
+#include "decision.h"                    // CcDecision, cc_decide (shared with distance.hip)
 
 #define CC_THREADS 256
 #define CC_TILE_H 32
@@ -46,27 +46,6 @@
 #define CC_TILE (CC_TILE_H * CC_TILE_W)
 #define CC_PER_THREAD (CC_TILE / CC_THREADS)
 #define CC_OUTSIDE 2                     // class of a tile cell outside the image
-
-struct CcDecision {
-  const void* pred;
-  int kind;                              // 0: fp32 with threshold, 1: uint8 (value != 0), 2: fp32 mask (((int)value) != 0)
-  float threshold;
-  int is_logits, invert;
-};
-
-__device__ __forceinline__ int cc_decide(const CcDecision& d, int i) {
-  int fg;
-  if (d.kind == 0) {
-    const float x = reinterpret_cast<const float*>(d.pred)[i];
-    const float p = d.is_logits ? 1.f / (1.f + expf(-x)) : x;          // (= sigmoid_f32 of step.hip, segmap_class of segmap.hip)
-    fg = p > d.threshold;
-  } else if (d.kind == 1) {
-    fg = reinterpret_cast<const unsigned char*>(d.pred)[i] != 0;
-  } else {
-    fg = ((int)reinterpret_cast<const float*>(d.pred)[i]) != 0;          // (how every kernel of the tail reads a mask)
-  }
-  return d.invert ? !fg : fg;
-}
 
 // ---- the local union-find of one tile (LDS) ------------------------------------------------------------------------------------
 __device__ __forceinline__ int cc_lds_find(int* lp, int i) {

@@ -27,6 +27,12 @@ specks and closes the pinholes of a stored split at the chosen threshold and han
     cleaned, stats = clean_prediction(pred, val["best_threshold"], min_area=8, max_hole=4)
     test = test_net(cleaned, val["best_threshold"]); objs = object_metrics(pred, val["best_threshold"], min_area=8)
 
+Distances (``hyperpri_amd.distance``, ``csrc/distance.hip``), opt-in too: ``surface_metrics`` reports Hausdorff, HD95, the average
+symmetric surface distance and surface Dice of a stored split from an exact integer distance transform, ``root_traits`` the length
+and diameter of the predicted and the true roots:
+
+    surf = surface_metrics(pred, val["best_threshold"], tolerances=(1.0, 2.0)); traits = root_traits(pred, val["best_threshold"])
+
 Lightning-free and torchmetrics-free like ``trainer.py``, whose device pieces this module composes (``hpri_bce_logits_fwd``,
 ``SegCounts``, ``PRCurve``, ``best_dice_threshold``, ``average_precision``); the maps are one kernel of their own
 (``csrc/segmap.hip``).  There is no CPU fallback: tensors must be fp32 on a ROCm device.
@@ -681,4 +687,73 @@ def object_metrics(pred: SplitPrediction, threshold: float, connectivity: int = 
     out: Dict[str, object] = dict(tot)
     out.update(object_precision=p, object_recall=r, object_f1=2 * p * r / (p + r) if p + r > 0 else nan,
                pred_areas=pred_areas, truth_areas=truth_areas)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# Distances (csrc/distance.hip, hyperpri_amd/distance.py): how far the predicted boundary lies from the true one, and the traits
+# ---------------------------------------------------------------------------------------------------
+def _mean_defined(values: Sequence[float]) -> float:
+    """The mean over the images that have a value (NaN = undefined, as the pixel metrics treat zero denominators)."""
+    v = np.asarray(values, dtype=np.float64)
+    ok = ~np.isnan(v)
+    return float(v[ok].mean()) if ok.any() else float("nan")
+
+
+def surface_metrics(pred: SplitPrediction, threshold: float, tolerances: Sequence[float] = (1.0, 2.0),
+                    min_area: int = 0) -> Dict[str, object]:
+    """Boundary distances over a stored split (``distance.surface_distances`` + ``surface_metrics_from_hist`` per group of
+    equal-sized images): the boundary of ``sigmoid(logits) > threshold`` (after ``clean_prediction(pred, threshold, min_area)`` when
+    ``min_area > 0``) against the boundary of the masks (``int(mask) != 0``).  Returns
+
+    * ``hd``, ``hd95``, ``assd`` and ``surface_dice`` (a dict over ``tolerances``): the means over the images that have a value;
+    * ``per_image``: the same keys as lists in the split's order, NaN where either map of an image has no boundary;
+    * ``images_undefined``: the number of such images; ``names``.
+
+    The distance transforms and histograms run on the device; one histogram per image and direction comes to the host."""
+    from . import distance as D
+    _require_cuda(pred.logits, "prediction to measure")
+    _require_device(pred.masks, "evaluation mask")
+    if int(min_area) > 0:
+        pred, threshold = clean_prediction(pred, threshold, min_area, 0)[0], 0.5
+    tol = [float(t) for t in tolerances]
+    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
+    per = {"hd": [], "hd95": [], "assd": [], "surface_dice": {t: [] for t in tol}}
+    undefined = 0
+    for i, j in _size_groups(pred):
+        a, b, (h, w) = pred.offsets[i], pred.offsets[j], pred.sizes[i]
+        sd = D.surface_distances(pred.logits[a:b].view(j - i, h, w), float(threshold), masks[a:b].view(j - i, h, w))
+        m = D.surface_metrics_from_hist(sd["hist"], tol)
+        undefined += m["images_undefined"]
+        for key in ("hd", "hd95", "assd"):
+            per[key].extend(float(v) for v in m[key])
+        for t in tol:
+            per["surface_dice"][t].extend(float(v) for v in m["surface_dice"][t])
+    out: Dict[str, object] = {key: _mean_defined(per[key]) for key in ("hd", "hd95", "assd")}
+    out["surface_dice"] = {t: _mean_defined(per["surface_dice"][t]) for t in tol}
+    out.update(per_image=per, images_undefined=undefined, names=list(pred.names))
+    return out
+
+
+def root_traits(pred: SplitPrediction, threshold: float, min_area: int = 0) -> Dict[str, object]:
+    """Root length and diameter over a stored split (``distance.root_traits`` per group of equal-sized images), for the prediction
+    ``sigmoid(logits) > threshold`` (after ``clean_prediction(pred, threshold, min_area)`` when ``min_area > 0``) and for the masks
+    (``int(mask) != 0``): per image, in the split's order, ``area``, ``skeleton_pixels``, ``links_straight``, ``links_diagonal``,
+    ``length_px``, ``diameter_mean_px``, ``diameter_median_px`` and ``diameter_hist``; the same keys of the masks under ``"truth"``;
+    ``names``."""
+    from . import distance as D
+    _require_cuda(pred.logits, "prediction to measure")
+    _require_device(pred.masks, "evaluation mask")
+    if int(min_area) > 0:
+        pred, threshold = clean_prediction(pred, threshold, min_area, 0)[0], 0.5
+    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
+    out: Dict[str, object] = {name: [] for name in D.TRAIT_NAMES}
+    out["truth"] = {name: [] for name in D.TRAIT_NAMES}
+    for i, j in _size_groups(pred):
+        a, b, (h, w) = pred.offsets[i], pred.offsets[j], pred.sizes[i]
+        t = D.root_traits(pred.logits[a:b].view(j - i, h, w), float(threshold), truth=masks[a:b].view(j - i, h, w))
+        for name in D.TRAIT_NAMES:
+            out[name].extend(t[name])
+            out["truth"][name].extend(t["truth"][name])
+    out["names"] = list(pred.names)
     return out

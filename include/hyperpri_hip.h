@@ -787,6 +787,46 @@ int hpri_cc_clean(const void* pred, int pred_kind, float threshold, int is_logit
                   int min_area, int max_hole, unsigned char* out, float* out_logits, float logit, long long* stats,
                   int* workspace, size_t ws_ints, hipStream_t stream);
 
+/* ---- distance transform, selection histogram, thinning (distance.hip; hyperpri_amd/distance.py, evaluate.py) ---------------
+ * Integers only; the atomics are integer adds and maxima on vector memory: every result is bit-reproducible.  pred, pred_kind,
+ * threshold, is_logits: the decision of hpri_cc_label; maps are contiguous (N, h, w), N*h*w < 2^31; images never influence each other.
+ *   hpri_edt            d2 (N, h, w) int32 = min(FAR, min over the sites q of the image of (y-qy)^2 + (x-qx)^2), FAR = h*h + w*w (an
+ *                       image without a site is FAR everywhere).  sites 0: the background pixels, 1: the foreground pixels, 2: the
+ *                       boundary -- foreground pixels with one of their four edge neighbours in the background or outside the image.
+ *                       A column pass (one thread per column, down then up, hpri_edt_col_threads columns per workgroup) and an
+ *                       in-place row pass (one workgroup of hpri_edt_row_threads threads per row, the row staged in LDS, an outward
+ *                       scan per pixel that stops at k^2 >= best).  hpri_edt_far (pure host) gives FAR, or -1 where the transform
+ *                       does not exist: a size <= 0, w > hpri_edt_max_width (the row's LDS budget), h*h + w*w >= 2^31.
+ *   hpri_select_stats   over the pixels p of image n that the selector picks (sel_kind 0: uint8 map, value != 0; 1: int32 map, value
+ *                       == 0, e.g. the sites of a distance transform) with values[p] >= 0:  stats[n*stats_stride] += their number,
+ *                       stats[n*stats_stride + 1] = max(itself, their largest value).  ACCUMULATED: the caller zeroes.
+ *   hpri_select_hist    hist[n*hist_stride + v] += 1 for each such pixel with v = values[p] < bins (a larger value is not counted).
+ *                       ACCUMULATED.  Reduced in LDS first where bins <= hpri_select_hist_lds_bins.
+ *   hpri_thin           Zhang-Suen thinning.  decide != 0: map = the uint8 decision of pred first (pairs = 0: only that).  Then
+ *                       `pairs` times sub-iteration 1 map -> other and sub-iteration 2 other -> map: with P2..P9 the neighbours
+ *                       clockwise from north (outside the image: background), B their sum and A the 0 -> 1 steps around the ring, a
+ *                       foreground pixel goes when 2 <= B <= 6, A == 1 and P2*P4*P6 == 0, P4*P6*P8 == 0 (sub-iteration 1) or
+ *                       P2*P4*P8 == 0, P2*P6*P8 == 0 (sub-iteration 2).  deleted[j*N + n] += pixels pair j took from image n
+ *                       (pairs * N int32, ACCUMULATED).  A pair that deletes nothing leaves map as it is: map is converged.
+ *   hpri_skeleton_links links[3n..3n+2] += S, E4, Ed of image n: skeleton pixels, horizontally or vertically adjacent pairs,
+ *                       diagonally adjacent pairs whose two common edge neighbours are both off the skeleton.  ACCUMULATED.
+ * Argument errors (a null pointer, a size <= 0, N*h*w >= 2^31, a kind, sites or sel_kind out of range, a row beyond
+ * hpri_edt_max_width, h*h + w*w >= 2^31, bins <= 0, a stride below its row) return -1 before any launch. */
+int hpri_edt_max_width(void);
+int hpri_edt_col_threads(void);
+int hpri_edt_row_threads(void);
+int hpri_edt_far(int h, int w);
+int hpri_select_hist_lds_bins(void);
+int hpri_edt(const void* pred, int pred_kind, float threshold, int is_logits, int sites, int N, int h, int w, int* d2,
+             hipStream_t stream);
+int hpri_select_stats(const int* values, const void* selector, int sel_kind, int N, int per_image, int* stats, int stats_stride,
+                      hipStream_t stream);
+int hpri_select_hist(const int* values, const void* selector, int sel_kind, int N, int per_image, int bins, int* hist,
+                     long long hist_stride, hipStream_t stream);
+int hpri_thin(const void* pred, int pred_kind, float threshold, int is_logits, int N, int h, int w, int decide, int pairs,
+              unsigned char* map, unsigned char* other, int* deleted, hipStream_t stream);
+int hpri_skeleton_links(const unsigned char* skeleton, int N, int h, int w, int* links, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
