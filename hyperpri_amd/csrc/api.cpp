@@ -30,6 +30,10 @@ extern "C" int hpri_version(void) { return 100; }  // 0.1.0
 //   wgrad_skip_edge       fp32 Winograd weight gradient: 1 = the strip that hangs over the right image edge runs only the MFMA
 //                         k-steps that hold a pixel column inside the image (the others multiply by zero-filled dY: bit-identical
 //                         results for finite activations, conv_wino.hip), 0 = all 8 k-steps of every strip  (HPRI_WGRAD_SKIP_EDGE, 1)
+//   wino4_fast_epilogue   fp32 Winograd convolution: 1 = a workgroup whose 16 x 8 pixels lie inside the image and whose 64 channels
+//                         are all written, in a launch without ReLU and accumulate, takes an epilogue without selects and with one
+//                         address per thread (same sums in the same order: bit-identical, conv_wino4.hip), 0 = every workgroup
+//                         takes the general epilogue                                          (HPRI_WINO4_FAST_EPILOGUE, 1)
 #include <stdlib.h>
 #include <atomic>
 #include <mutex>
@@ -37,14 +41,14 @@ extern "C" int hpri_version(void) { return 100; }  // 0.1.0
 // autograd's worker threads): the options are atomics initialised exactly once, from the environment, under std::call_once;
 // hpri_set_option stores with release order and the launchers' reads are relaxed loads of an int (a plan option changes
 // block order only, never results).
-static std::atomic<int> g_opt[7];
+static std::atomic<int> g_opt[8];
 static std::once_flag g_opt_once;
-static const char* const g_opt_name[7] = {"conv_nbx_min", "wgrad_xcd_min_tiles", "wgrad_xcd_min_strips", "bf16v3_tile_width", "bn_wide_cq", "wgrad_cu_reserve", "wgrad_skip_edge"};
-static const char* const g_opt_env[7] = {"HPRI_NBX_MIN", "HPRI_WGRAD_XCD_MIN", "HPRI_WGRAD_XCD_STRIPS", "HPRI_V3_TILE_WIDTH", "HPRI_BN_WIDE_CQ", "HPRI_WGRAD_CU_RESERVE", "HPRI_WGRAD_SKIP_EDGE"};
-static const int g_opt_default[7] = {9, 128, 2048, 0, 1, 0, 1};
+static const char* const g_opt_name[8] = {"conv_nbx_min", "wgrad_xcd_min_tiles", "wgrad_xcd_min_strips", "bf16v3_tile_width", "bn_wide_cq", "wgrad_cu_reserve", "wgrad_skip_edge", "wino4_fast_epilogue"};
+static const char* const g_opt_env[8] = {"HPRI_NBX_MIN", "HPRI_WGRAD_XCD_MIN", "HPRI_WGRAD_XCD_STRIPS", "HPRI_V3_TILE_WIDTH", "HPRI_BN_WIDE_CQ", "HPRI_WGRAD_CU_RESERVE", "HPRI_WGRAD_SKIP_EDGE", "HPRI_WINO4_FAST_EPILOGUE"};
+static const int g_opt_default[8] = {9, 128, 2048, 0, 1, 0, 1, 1};
 
 static void opt_init() {
-  for (int i = 0; i < 7; ++i) {
+  for (int i = 0; i < 8; ++i) {
     const char* e = getenv(g_opt_env[i]);
     int v = e ? atoi(e) : g_opt_default[i];
     if (v < 0) v = g_opt_default[i];
@@ -59,7 +63,7 @@ int hpri_option(int idx) {
 
 extern "C" int hpri_set_option(const char* name, int value) {
   std::call_once(g_opt_once, opt_init);
-  for (int i = 0; i < 7; ++i)
+  for (int i = 0; i < 8; ++i)
     if (name && strcmp(name, g_opt_name[i]) == 0) {
       if (value < 0) return hpri_set_error(HPRI_ERR_ARG, "set_option: value must be >= 0");
       g_opt[i].store(value, std::memory_order_release);
@@ -126,7 +130,7 @@ extern "C" int hpri_set_loss_scale(float scale) {
 }
 
 extern "C" int hpri_get_option(const char* name) {
-  for (int i = 0; i < 7; ++i)
+  for (int i = 0; i < 8; ++i)
     if (name && strcmp(name, g_opt_name[i]) == 0) return hpri_option(i);
   return hpri_set_error(HPRI_ERR_ARG, "get_option: unknown option");
 }

@@ -52,7 +52,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
   } while (0)
 
 int hpri_set_error(int code, const char* msg);
-int hpri_option(int idx);   // 0 conv_nbx_min, 1 wgrad_xcd_min_tiles, 2 wgrad_xcd_min_strips, 3 bf16v3_tile_width, 4 bn_wide_cq, 5 wgrad_cu_reserve, 6 wgrad_skip_edge (api.cpp; thread-safe)
+int hpri_option(int idx);   // 0 conv_nbx_min, 1 wgrad_xcd_min_tiles, 2 wgrad_xcd_min_strips, 3 bf16v3_tile_width, 4 bn_wide_cq, 5 wgrad_cu_reserve, 6 wgrad_skip_edge, 7 wino4_fast_epilogue (api.cpp; thread-safe)
 int hpri_cu_count();        // compute units of the current device (api.cpp; cached)
 float hpri_loss_scale();    // the calling thread's loss scale (hpri_set_loss_scale; 1 unless set)
 
@@ -93,11 +93,19 @@ typedef __amdgpu_buffer_rsrc_t hpri_rsrc_t;
 #define HPRI_LDS_DMA16(rs_, lds_, voff_, soff_) \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (__attribute__((address_space(3))) void*)(lds_), 16, voff_, soff_, 0, 0)
 #define HPRI_BUFFER_LOAD_F32(rs_, voff_, soff_) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_, voff_, soff_, 0))
+// 16 bytes per lane at base + soffset + voffset, no LDS: one 32-bit per-lane offset serves every access that differs from it
+// by a wave-uniform amount (soffset lives in an SGPR)
+typedef unsigned hpri_u32x4 __attribute__((ext_vector_type(4)));
+#define HPRI_BUFFER_LOAD_F32X4(rs_, voff_, soff_) __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_, voff_, soff_, 0))
+#define HPRI_BUFFER_STORE_F32X4(v_, rs_, voff_, soff_) \
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(hpri_u32x4, v_), rs_, voff_, soff_, 0)
 #else
 typedef int hpri_rsrc_t;
 #define HPRI_MAKE_RSRC(ptr_, bytes_) 0
 #define HPRI_LDS_DMA16(rs_, lds_, voff_, soff_) ((void)(rs_))
 #define HPRI_BUFFER_LOAD_F32(rs_, voff_, soff_) 0.f
+#define HPRI_BUFFER_LOAD_F32X4(rs_, voff_, soff_) (f32x4{0.f, 0.f, 0.f, 0.f})
+#define HPRI_BUFFER_STORE_F32X4(v_, rs_, voff_, soff_) ((void)(rs_))
 #endif
 
 // ---- item queues of the persistent kernels (conv_bf16v3, gemm_bf16v3, gemm_f32v2) ----------------------------------------------

@@ -35,6 +35,7 @@ struct Wino4Args {
   int N, H, W, Cin_pad, Cout, Cout_pad, y_cw, accumulate, relu;
   int tiles_x, tiles_y;
   int items, per_xcd, banded;   // work items (pixel tiles x channel blocks), items per XCD band, item order (below)
+  int fast;                     // option wino4_fast_epilogue and a launch it applies to (host); the kernel adds the per-tile conditions
   int ncu, stagger_cycles;      // compute units of the device (host: hipDeviceProp_t.multiProcessorCount) and the one-off delay of
                                 // each CU's second occupant (below); 0 cycles = no stagger
 #ifdef HPRI_STAMPS
@@ -67,6 +68,194 @@ struct Wino4Args {
 // LDS cycle: up to 4-way)
 #define W4_SWZ(slot_, hy_) ((((slot_) >> 1) + (hy_)) & 7)
 
+// ---- second half of the epilogue: the exchange planes are in LDS (ex[8 = 2 a + j][32 tiles][64 ch], frequency row 2 without
+// its sign); thread (tid>>4, oq = tid&15) owns tiles ot = (tid>>4) + 16 it and channels 4 oq .. 4 oq + 3: row transform, bias,
+// store, statistics / BatchNorm-backward partial sums.
+//   FAST   all 16 x 8 pixels inside the image, all 64 channels written, no ReLU, no accumulate (checked once per workgroup by
+//          the caller): no select, no fmaxf, and ONE 32-bit offset per thread against a descriptor at the tile's origin -- the
+//          thread's 8 pixels (and the pre-BN loads at the same pixels) differ by wave-uniform amounts that go in as soffset
+//   !FAST  the general form with every mask
+// Both forms add the same numbers in the same order.  The reduction scratch lies BEHIND the 64 KB of planes (W4_RED: 14 KB are
+// left), with one area per statistics pass, so no barrier waits for the planes' readers or for the previous pass's.
+#define W4_RED (8 * 32 * 64 * 4)
+template <bool FAST>
+__device__ __forceinline__ void w4_epilogue(const Wino4Args& a, unsigned char* smem, const f32x4 bias4, const int img, const int bx,
+                                            const int nb, const int Y0, const int X0) {
+  const int tid = threadIdx.x;
+  const float* ex = reinterpret_cast<const float*>(smem);
+  static_assert(W4_RED + 2 * 16 * 64 * 4 + 256 <= 2 * W4_A_BYTES + 4 * W4_B_WAVE, "reduction scratch must fit behind the planes");
+  STAMP(5)
+  const int oq = tid & 15;
+  const int n0 = nb * 64 + oq * 4;
+  f32x4 outv[2][4];                                 // [item][pixel] x 4 channels
+  const int vrows = FAST ? 8 : min(8, a.H - Y0), vcols = FAST ? 16 : min(16, a.W - X0);
+  // FAST: the thread's first pixel (2 (tid>>7), 2 ((tid>>4)&7)) of the tile, pixel (it, k) = + (4 it + (k>>1)) rows + (k&1) columns
+  const int py0 = 2 * (tid >> 7), px0 = 2 * ((tid >> 4) & 7);
+  // accumulate (a skip gradient already holds the other producer's part): ALL old values are loaded before the first store
+  // -- a load behind a store waits for the store as well (vmcnt counts in order)
+  f32x4 oldv[2][4];
+  if (!FAST && a.accumulate) {
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int ot = (tid >> 4) + 16 * it;
+      const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int yy = py + (k >> 1), xx = px + (k & 1);
+        const bool ok = yy < vrows && xx < vcols && n0 < a.y_cw;
+        const float* src = a.y + ((size_t)(img * a.H + Y0 + min(yy, vrows - 1)) * a.W + X0 + min(xx, vcols - 1)) * a.y_cs + a.y_coff + min(n0, a.y_cw - 4);
+        const f32x4 t = *reinterpret_cast<const f32x4*>(src);
+        oldv[it][k] = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  const hpri_rsrc_t rs_y = HPRI_MAKE_RSRC(a.y + ((size_t)(img * a.H + Y0) * a.W + X0) * a.y_cs + a.y_coff + nb * 64,
+                                          ((7 * a.W + 15) * a.y_cs + 64) * 4);
+  const unsigned yo = (unsigned)((py0 * a.W + px0) * a.y_cs + oq * 4) * 4u;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    const int ot = (tid >> 4) + 16 * it;            // tile of the workgroup: (ot>>3, ot&7)
+    f32x4 m[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) m[i][j] = *reinterpret_cast<const f32x4*>(ex + ((i * 2 + j) * 32 + ot) * 64 + oq * 4);
+    // Y = A^T Z with A^T = [1 1 1 0; 0 1 -1 -1]; m[2] is stored as -Z2: x + (-z) and x - z are the same bits
+    f32x4 o[4] = {m[0][0] + m[1][0] - m[2][0], m[0][1] + m[1][1] - m[2][1], m[1][0] + m[2][0] - m[3][0], m[1][1] + m[2][1] - m[3][1]};
+    const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      f32x4 v = o[k] + bias4;
+      if (FAST) {
+        HPRI_BUFFER_STORE_F32X4(v, rs_y, yo, ((4 * it + (k >> 1)) * a.W + (k & 1)) * a.y_cs * 4);
+        outv[it][k] = v;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          if (a.relu) v[c] = fmaxf(v[c], 0.f);
+          if (n0 + c >= a.Cout) v[c] = 0.f;
+        }
+        const int yy = py + (k >> 1), xx = px + (k & 1);
+        const bool ok = yy < vrows && xx < vcols;
+        if (ok && n0 < a.y_cw) {
+          float* dst = a.y + ((size_t)(img * a.H + Y0 + yy) * a.W + X0 + xx) * a.y_cs + a.y_coff + n0;
+          if (a.accumulate) v += oldv[it][k];
+          *reinterpret_cast<f32x4*>(dst) = v;
+        }
+        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+        outv[it][k] = ok ? v : zero4;
+      }
+    }
+  }
+  STAMP(2)
+  float* red = reinterpret_cast<float*>(smem + W4_RED);
+  if (a.stats != nullptr) {
+    // two-pass per-tile statistics over the valid pixels: thread (tid>>4, oq) holds 8 pixels of channels 4 oq .. 4 oq + 3.
+    // red: pass 0 [16][64 ch] + [64] means, pass 1 [16][64 ch] behind them
+    const float cnt = (float)(vrows * vcols);
+    f32x4 mean4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      float* rp = red + pass * (17 * 64);
+      f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int it = 0; it < 2; ++it) {
+        const int ot = (tid >> 4) + 16 * it;
+        const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const bool ok = FAST || ((py + (k >> 1)) < vrows && (px + (k & 1)) < vcols);
+          if (pass == 0) sacc += outv[it][k];
+          else if (ok) {                          // explicit FMAs, in pixel order: a contraction the compiler picks may differ between the forms
+            const f32x4 d = outv[it][k] - mean4;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) sacc[c] = __builtin_fmaf(d[c], d[c], sacc[c]);
+          }
+        }
+      }
+      *reinterpret_cast<f32x4*>(rp + (tid >> 4) * 64 + oq * 4) = sacc;
+      __syncthreads();
+      if (tid < 64) {                               // channel c = tid: sum over the 16 thread rows
+        float tsum = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) tsum += rp[q * 64 + tid];
+        if (pass == 0) red[16 * 64 + tid] = tsum / cnt;
+        else a.stats[(size_t)bx * a.Cout_pad + nb * 64 + tid] = make_float4(red[16 * 64 + tid], tsum, cnt, 0.f);
+      }
+      if (pass == 0) {
+        __syncthreads();
+        mean4 = *reinterpret_cast<const f32x4*>(red + 16 * 64 + oq * 4);
+      }
+    }
+  }
+  if (a.bn_part != nullptr) {
+    // BatchNorm-backward partial sums of this tile (see Wino4Args): thread (tid>>4, oq) holds g at 8 pixels x 4 channels
+    f32x4 sc4, sh4, mu4, is4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int n = FAST ? n0 + c : min(n0 + c, a.Cout - 1);
+      sc4[c] = a.bn_scale[n]; sh4[c] = a.bn_shift[n]; mu4[c] = a.bn_mean[n]; is4[c] = a.bn_invstd[n];
+    }
+    f32x4 xv[2][4];
+    const hpri_rsrc_t rs_x = HPRI_MAKE_RSRC(a.bn_x + ((size_t)(img * a.H + Y0) * a.W + X0) * a.bn_x_cs + a.bn_x_coff + nb * 64,
+                                            ((7 * a.W + 15) * a.bn_x_cs + 64) * 4);
+    const unsigned xo = (unsigned)((py0 * a.W + px0) * a.bn_x_cs + oq * 4) * 4u;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int ot = (tid >> 4) + 16 * it;
+      const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (FAST) {
+          xv[it][k] = HPRI_BUFFER_LOAD_F32X4(rs_x, xo, ((4 * it + (k >> 1)) * a.W + (k & 1)) * a.bn_x_cs * 4);
+        } else {
+          const int yy = min(py + (k >> 1), vrows - 1), xx = min(px + (k & 1), vcols - 1);
+          xv[it][k] = *reinterpret_cast<const f32x4*>(a.bn_x + ((size_t)(img * a.H + Y0 + yy) * a.W + X0 + xx) * a.bn_x_cs + a.bn_x_coff +
+                                                      min(n0, a.Cout_pad - 4));
+        }
+      }
+    }
+    f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f};
+    // outv is zero outside the image and beyond Cout, so those positions add nothing; bn_relu is tested once, not per element.
+    // The FMAs are written out (BN(x) and the xhat term), so both forms fuse the same products.
+    if (a.bn_relu) {
+#pragma unroll
+      for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const float gj = (__builtin_fmaf(xv[it][k][c], sc4[c], sh4[c]) > 0.f) ? outv[it][k][c] : 0.f;
+            t1[c] += gj;
+            t2[c] = __builtin_fmaf(gj, (xv[it][k][c] - mu4[c]) * is4[c], t2[c]);
+          }
+    } else {
+#pragma unroll
+      for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const float gj = outv[it][k][c];
+            t1[c] += gj;
+            t2[c] = __builtin_fmaf(gj, (xv[it][k][c] - mu4[c]) * is4[c], t2[c]);
+          }
+    }
+    *reinterpret_cast<f32x4*>(red + (tid >> 4) * 64 + oq * 4) = t1;                        // [2][16][64 ch]
+    *reinterpret_cast<f32x4*>(red + 1024 + (tid >> 4) * 64 + oq * 4) = t2;
+    __syncthreads();
+    if (tid < 128) {                                // (sum, channel) = (tid >> 6, tid & 63): fixed order over the 16 thread rows
+      const int which = tid >> 6, c = tid & 63;
+      float tsum = 0.f;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) tsum += red[which * 1024 + q * 64 + c];
+      if (nb * 64 + c < a.bn_cpart) a.bn_part[((size_t)bx * 2 + which) * a.bn_cpart + nb * 64 + c] = tsum;
+    }
+  }
+  STAMP(3)
+}
+
+
 __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(Wino4Args a) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * W4_A_BYTES + 4 * W4_B_WAVE];
   unsigned char* b_lds = smem + 2 * W4_A_BYTES;
@@ -94,8 +283,12 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(Wino4Args a) {
 
   // B^T row fa: two input rows r1, r2:  a=0: d0 - d2 | a=1: d1 + d2 | a=2: d2 - d1 | a=3: d1 - d3   (= s1 (d[r1] + sigma d[r2]))
   const int r1 = (fa == 0) ? 0 : 1, r2 = (fa == 3) ? 3 : 2;
-  const float s1 = (fa == 2) ? -1.f : 1.f, s2 = (fa == 1 || fa == 2) ? 1.f : -1.f;
-  const float sigma = s1 * s2;
+  // -1 the compiler cannot see through: x + mone * y is ONE packed instruction for two channels (v_pk_fma_f32, as P below), a plain
+  // x - y is scalarized into v_sub_f32 (12 instead of 6 instructions per stage).  fma(y, -1, x) and x - y round the same number once.
+  int mone_bits = 0xBF800000;
+  asm volatile("" : "+s"(mone_bits));
+  const float mone = __builtin_bit_cast(float, mone_bits);
+  const float sigma = (fa == 1) ? 1.f : -1.f;    // s1 s2 with s1 = (fa == 2 ? -1 : 1), s2 = (fa == 1 || fa == 2 ? 1 : -1)
 
   // ---- halo DMA (buffer_load ... lds): instruction i covers slots [8i, 8i+8); lane -> slot 8i + (lane>>3), physical quad
   //      lane&7.  The per-lane byte offset goes in as the 32-bit voffset of a buffer descriptor over this image; pixels outside
@@ -244,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(Wino4Args a) {
         const f32x4 d2 = *reinterpret_cast<const f32x4*>(smem + ((pre[2 * c + 1] ^ q16) + aboff));
         P[c] = d1 + sigma * d2;
       }
-      const f32x4 v[4] = {P[0] - P[2], P[1] + P[2], P[2] - P[1], P[1] - P[3]};
+      const f32x4 v[4] = {P[0] + mone * P[2], P[1] + P[2], P[2] + mone * P[1], P[1] + mone * P[3]};
 #ifndef WINO4_NO_SETPRIO
       __builtin_amdgcn_s_setprio(1);
 #endif
@@ -271,153 +464,26 @@ __global__ __launch_bounds__(256, 2) void conv_wino4_kernel(Wino4Args a) {
   // acc[b][nt][r]: tile t = (r&3) + 8*(r>>2) + 4*lh, channel nt*32 + li, frequency (fa, b), without the row sign s1.
   // Column transform in registers: Z[.][0] = M0 + M1 + M2, Z[.][1] = M1 - M2 - M3; the 4 x 2 planes meet in LDS (64 KB), then
   // every thread owns two (tile, channel quad) pairs: 8 float4 reads each, the row transform, bias, 2x2 pixels as float4.
+  // The planes of frequency row 2 go through LDS WITHOUT their sign s1 = -1: the reader subtracts them (w4_epilogue).
   float* ex = reinterpret_cast<float*>(smem);       // [8 = 2 a + j][32 tiles][64 ch]
   static_assert(8 * 32 * 64 * 4 <= 2 * W4_A_BYTES + 4 * W4_B_WAVE, "exchange buffer must fit the staging LDS");
+  float* exw = ex + ((fa * 2) * 32 + 4 * lh) * 64 + li;      // one address per lane; plane j, tile and channel group are immediates
 #pragma unroll
   for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int t = (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int t = (r & 3) + 8 * (r >> 2);         // + 4 lh
       const float m0 = acc[0][nt][r], m1 = acc[1][nt][r], m2 = acc[2][nt][r], m3 = acc[3][nt][r];
-      ex[((fa * 2 + 0) * 32 + t) * 64 + nt * 32 + li] = s1 * (m0 + m1 + m2);
-      ex[((fa * 2 + 1) * 32 + t) * 64 + nt * 32 + li] = s1 * (m1 - m2 - m3);
+      exw[(0 * 32 + t) * 64 + nt * 32] = m0 + m1 + m2;
+      exw[(1 * 32 + t) * 64 + nt * 32] = m1 - m2 - m3;
     }
   STAMP(4)
   __syncthreads();
-  STAMP(5)
-  const int oq = tid & 15;
-  const int n0 = nb * 64 + oq * 4;
-  f32x4 outv[2][4];                                 // [item][pixel] x 4 channels
-  const int vrows = min(8, a.H - Y0), vcols = min(16, a.W - X0);
-  // accumulate (a skip gradient already holds the other producer's part): ALL old values are loaded before the first store
-  // -- a load behind a store waits for the store as well (vmcnt counts in order)
-  f32x4 oldv[2][4];
-  if (a.accumulate) {
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int ot = (tid >> 4) + 16 * it;
-      const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int yy = py + (k >> 1), xx = px + (k & 1);
-        const bool ok = yy < vrows && xx < vcols && n0 < a.y_cw;
-        const float* src = a.y + ((size_t)(img * a.H + Y0 + min(yy, vrows - 1)) * a.W + X0 + min(xx, vcols - 1)) * a.y_cs + a.y_coff + min(n0, a.y_cw - 4);
-        const f32x4 t = *reinterpret_cast<const f32x4*>(src);
-        oldv[it][k] = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-  }
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int ot = (tid >> 4) + 16 * it;            // tile of the workgroup: (ot>>3, ot&7)
-    f32x4 m[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) m[i][j] = *reinterpret_cast<const f32x4*>(ex + ((i * 2 + j) * 32 + ot) * 64 + oq * 4);
-    // Y = A^T Z with A^T = [1 1 1 0; 0 1 -1 -1]
-    f32x4 o[4] = {m[0][0] + m[1][0] + m[2][0], m[0][1] + m[1][1] + m[2][1], m[1][0] - m[2][0] - m[3][0], m[1][1] - m[2][1] - m[3][1]};
-    const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      f32x4 v = o[k] + bias4;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        if (a.relu) v[c] = fmaxf(v[c], 0.f);
-        if (n0 + c >= a.Cout) v[c] = 0.f;
-      }
-      const int yy = py + (k >> 1), xx = px + (k & 1);
-      const bool ok = yy < vrows && xx < vcols;
-      if (ok && n0 < a.y_cw) {
-        float* dst = a.y + ((size_t)(img * a.H + Y0 + yy) * a.W + X0 + xx) * a.y_cs + a.y_coff + n0;
-        if (a.accumulate) v += oldv[it][k];
-        *reinterpret_cast<f32x4*>(dst) = v;
-      }
-      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-      outv[it][k] = ok ? v : zero4;
-    }
-  }
-  STAMP(2)
-  if (a.stats != nullptr) {
-    // two-pass per-tile statistics over the valid pixels: thread (tid>>4, oq) holds 8 pixels of channels 4 oq .. 4 oq + 3
-    __syncthreads();                                // everyone has read the exchange planes
-    float* red = reinterpret_cast<float*>(smem);    // [16][64 ch] + [64] means
-    const float cnt = (float)(vrows * vcols);
-    f32x4 mean4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      f32x4 sacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int ot = (tid >> 4) + 16 * it;
-        const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const bool ok = (py + (k >> 1)) < vrows && (px + (k & 1)) < vcols;
-          if (pass == 0) sacc += outv[it][k];
-          else if (ok) { const f32x4 d = outv[it][k] - mean4; sacc += d * d; }
-        }
-      }
-      *reinterpret_cast<f32x4*>(red + (tid >> 4) * 64 + oq * 4) = sacc;
-      __syncthreads();
-      if (tid < 64) {                               // channel c = tid: sum over the 16 thread rows
-        float tsum = 0.f;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) tsum += red[q * 64 + tid];
-        if (pass == 0) red[16 * 64 + tid] = tsum / cnt;
-        else a.stats[(size_t)bx * a.Cout_pad + nb * 64 + tid] = make_float4(red[16 * 64 + tid], tsum, cnt, 0.f);
-      }
-      __syncthreads();
-      if (pass == 0) mean4 = *reinterpret_cast<const f32x4*>(red + 16 * 64 + oq * 4);
-      __syncthreads();
-    }
-  }
-  if (a.bn_part != nullptr) {
-    // BatchNorm-backward partial sums of this tile (see Wino4Args): thread (tid>>4, oq) holds g at 8 pixels x 4 channels
-    f32x4 sc4, sh4, mu4, is4;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int n = min(n0 + c, a.Cout - 1);
-      sc4[c] = a.bn_scale[n]; sh4[c] = a.bn_shift[n]; mu4[c] = a.bn_mean[n]; is4[c] = a.bn_invstd[n];
-    }
-    f32x4 xv[2][4];
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int ot = (tid >> 4) + 16 * it;
-      const int py = 2 * (ot >> 3), px = 2 * (ot & 7);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int yy = min(py + (k >> 1), vrows - 1), xx = min(px + (k & 1), vcols - 1);
-        xv[it][k] = *reinterpret_cast<const f32x4*>(a.bn_x + ((size_t)(img * a.H + Y0 + yy) * a.W + X0 + xx) * a.bn_x_cs + a.bn_x_coff +
-                                                    min(n0, a.Cout_pad - 4));
-      }
-    }
-    f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int it = 0; it < 2; ++it)
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          // outv is zero outside the image and beyond Cout, so those positions add nothing
-          const float gj = (!a.bn_relu || (xv[it][k][c] * sc4[c] + sh4[c] > 0.f)) ? outv[it][k][c] : 0.f;
-          t1[c] += gj;
-          t2[c] += gj * ((xv[it][k][c] - mu4[c]) * is4[c]);
-        }
-    __syncthreads();                                // everyone has read the exchange planes (and the statistics scratch)
-    float* red = reinterpret_cast<float*>(smem);    // [2][16][64 ch]
-    *reinterpret_cast<f32x4*>(red + (tid >> 4) * 64 + oq * 4) = t1;
-    *reinterpret_cast<f32x4*>(red + 1024 + (tid >> 4) * 64 + oq * 4) = t2;
-    __syncthreads();
-    if (tid < 128) {                                // (sum, channel) = (tid >> 6, tid & 63): fixed order over the 16 thread rows
-      const int which = tid >> 6, c = tid & 63;
-      float tsum = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) tsum += red[which * 1024 + q * 64 + c];
-      if (nb * 64 + c < a.bn_cpart) a.bn_part[((size_t)bx * 2 + which) * a.bn_cpart + nb * 64 + c] = tsum;
-    }
-  }
-  STAMP(3)
+  // One wave-uniform choice per workgroup (Wino4Args.fast): a tile inside the image with a full channel block, in a launch
+  // without ReLU and accumulate, needs none of the general epilogue's selects.
+  const bool fast = a.fast != 0 && a.H - Y0 >= 8 && a.W - X0 >= 16 && nb * 64 + 64 <= min(a.Cout, a.y_cw);
+  if (fast) w4_epilogue<true>(a, smem, bias4, img, bx, nb, Y0, X0);
+  else w4_epilogue<false>(a, smem, bias4, img, bx, nb, Y0, X0);
 }
 
 // ---- filter transform: U = G g G^T, packed with k innermost: [Cin_pad/8][16][Ncols_pad][8] ---------------------------------
@@ -525,6 +591,10 @@ static int wino4_launch(const float* x, int x_cs, int x_coff, const float* up, c
                  "conv_wino4_bnred: the pre-BN view must be float4-aligned and hold Cout_pad channels");
     HPRI_REQUIRE(bn_cpart >= Cout && bn_cpart % 4 == 0, "conv_wino4_bnred: partial width must cover the channels");
   }
+  // fast epilogue (w4_epilogue<true>): no ReLU, no accumulate, and eight image rows of the output (and pre-BN) view within reach
+  // of a 32-bit byte offset from the tile's origin
+  a.fast = hpri_option(7) != 0 && accumulate == 0 && (8ll * W + 16) * y_cs * 4 < 0x7FFFFF00ll &&
+           (bn_part == nullptr || (8ll * W + 16) * bn_x_cs * 4 < 0x7FFFFF00ll);
   a.ncu = hpri_cu_count(); a.stagger_cycles = W4_STAGGER_CYCLES;
 #ifdef HPRI_STAMPS
   a.stamps = hpri_wino4_stamps;

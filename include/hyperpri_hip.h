@@ -49,7 +49,10 @@ int hpri_version(void);
  * on them, only block order and (for weight gradients) the number of partial slabs, i.e. the summation order.
  * "wgrad_skip_edge" (default 1): the fp32 Winograd weight gradient leaves out the MFMA k-steps whose four pixel columns all lie
  * right of the image edge, where dY is zero-filled; 0 runs every k-step of every strip.  Bit-identical results for finite
- * activations (a non-finite activation in the column beyond the edge-most valid one gives NaN only with 0). */
+ * activations (a non-finite activation in the column beyond the edge-most valid one gives NaN only with 0).
+ * "wino4_fast_epilogue" (default 1): workgroups of hpri_conv_wino4 / hpri_conv_wino4_bnred whose 16 x 8 pixels lie inside the image
+ * and whose 64 channels are all written take, in launches without ReLU and accumulate, an epilogue without per-element selects; 0
+ * sends every workgroup through the general epilogue.  Bit-identical results. */
 int hpri_set_option(const char* name, int value);
 /* A non-blocking stream of the lowest priority the current device offers (*priority receives it); the caller owns it. */
 

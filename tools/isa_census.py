@@ -9,7 +9,11 @@ Second form, for a kernel with several k loops (conv_wino_wgrad_kernel: one per 
     isa_census.py --loops conv_wino.hip conv_wino_wgrad_kernel [mfmas_per_k_step] [--source FILE]
 lists every innermost single-block loop that holds an MFMA, in the order of the listing: MFMAs, vector instructions by mnemonic,
 LDS instructions by mnemonic, waits, per k-step (the loop's MFMAs / mfmas_per_k_step, default 8), what the loop around it holds
-outside the k loop (the per-unit bookkeeping, counted statically), and the kernel's registers and scratch.  --source compiles another copy of the file (the parent's, say) with csrc/ as the include directory."""
+outside the k loop (the per-unit bookkeeping, counted statically), and the kernel's registers and scratch.  --source compiles another copy of the file (the parent's, say) with csrc/ as the include directory.
+
+Third form, conv_wino4_kernel (its stage loop spans several basic blocks):
+    isa_census.py --wino4 [--source FILE]
+gives the stage loop per 32 MFMAs and the epilogue by phase (wino4_census)."""
 import json
 import os
 import re
@@ -98,6 +102,84 @@ def loops_census(argv):
                       "scratch_bytes": meta("private_seg_size"), "mfma_loops": rows}, indent=1))
 
 
+def wino4_census(argv):
+    """conv_wino4_kernel: its stage loop spans several basic blocks (wave-uniform branches around the DMA issue), so --loops does
+    not see it.  Stage loop: the blocks hipcc marks as part of a loop that holds MFMAs, per 32 MFMAs (one stage of one wave).  Epilogue: the
+    diagnostics build (-DHPRI_STAMPS) carries an s_memtime at every STAMP; behind the last MFMA they come in source order -- 1, 4,
+    then 5, 2, 3 once per epilogue variant -- and cut the listing into exchange | row transform + store | statistics + partial
+    sums.  A static count: both sides of every branch inside a phase are counted once."""
+    source = None
+    if "--source" in argv:
+        i = argv.index("--source")
+        source = argv[i + 1]
+    csrc = os.path.join(ROOT, "hyperpri_amd", "csrc")
+    kern = "conv_wino4_kernel"
+
+    def listing(extra):
+        with tempfile.TemporaryDirectory() as td:
+            out = os.path.join(td, "k.s")
+            subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-S", "--cuda-device-only",
+                                   *extra, "-I", csrc, source or os.path.join(csrc, "conv_wino4.hip"), "-o", out], stderr=subprocess.DEVNULL)
+            text = open(out).read()
+        m = re.search(r"^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\.Lfunc_end" % kern, text, re.S | re.M)
+        name, body = m.group(1), m.group(2)
+        ins = [ln.split(";")[0].split()[0] for ln in body.splitlines() if ln.startswith("\t") and not ln.strip().startswith((";", "."))]
+        meta = {k: int(re.search(r"\.set %s\.%s, (\d+)" % (re.escape(name), k), text).group(1)) for k in ("num_vgpr", "private_seg_size")}
+        meta["lds_bytes"] = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", text).group(1))
+        return name, ins, meta, body
+
+    def count(xs):
+        valu = [re.sub(r"_e32$|_e64$", "", x) for x in xs if x.startswith("v_") and not x.startswith("v_mfma")]
+        by = {}
+        for x in valu:
+            by[x] = by.get(x, 0) + 1
+        return {"vector": len(valu), "lds": sum(x.startswith("ds_") for x in xs),
+                "memory": sum(x.startswith(("buffer_", "global_", "flat_")) for x in xs), "barriers": sum(x == "s_barrier" for x in xs),
+                "mfma": sum(x.startswith("v_mfma") for x in xs), "vector_by_mnemonic": dict(sorted(by.items()))}
+
+    name, ins, meta, body = listing([])
+    # blocks by the loop that holds them: hipcc names it in the comment of every block label
+    groups, cur = {}, None
+    for ln in body.splitlines():
+        lab = re.match(r"^(\.LBB\d+_\d+):(.*)", ln) or re.match(r"^; (%bb\.\d+):(.*)", ln)
+        if lab:
+            note = lab.group(2)
+            hdr = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d)", note)
+            own = re.search(r"This (?:Inner )?Loop Header: Depth=(\d)", note)
+            cur = (hdr.group(1), int(hdr.group(2))) if hdr else (lab.group(1)[2:], int(own.group(1))) if own else None
+            continue
+        if cur and ln.startswith("\t") and not ln.strip().startswith((";", ".")):
+            groups.setdefault(cur, []).append(ln.split(";")[0].split()[0])
+    loops = {}
+    for (hdr, depth), xs in groups.items():
+        c = count(xs)
+        if c["mfma"]:
+            what = "steady stages (inner loop %s)" % hdr if depth == 2 else "first stage of a chunk and the halo DMA issue (chunk loop %s outside its inner loop)" % hdr
+            loops[what] = {"stages_in_the_listing": c["mfma"] / 32.0, "vector_per_stage": round(c["vector"] / (c["mfma"] / 32.0), 2),
+                           "lds_per_stage": round(c["lds"] / (c["mfma"] / 32.0), 2), **c}
+    last = len(ins) - 1 - next(i for i, x in enumerate(reversed(ins)) if x.startswith("v_mfma"))
+    whole = count(ins[last + 1:])
+    _, dins, _, _ = listing(["-DHPRI_STAMPS"])
+    dlast = len(dins) - 1 - next(i for i, x in enumerate(reversed(dins)) if x.startswith("v_mfma"))
+    cuts = [i for i in range(dlast + 1, len(dins)) if dins[i] == "s_memtime"]
+    assert len(cuts) >= 5 and (len(cuts) - 2) % 3 == 0, f"{len(cuts)} stamps behind the last MFMA"
+    phases = {"exchange (column transform, plane writes)": count(dins[cuts[0]:cuts[1]])}
+    for v in range((len(cuts) - 2) // 3):
+        c5, c2, c3 = cuts[2 + 3 * v: 5 + 3 * v]
+        store = count(dins[c5:c2])
+        tag = "fast" if "buffer_store_dwordx4" in dins[c5:c2] else "general"
+        phases[f"{tag}: row transform, bias, store (and the accumulate preload)"] = store
+        phases[f"{tag}: statistics and BatchNorm-backward partial sums"] = count(dins[c2:c3])
+    print(json.dumps({"kernel": name, "source": source or "conv_wino4.hip", "vgprs": meta["num_vgpr"], "scratch_bytes": meta["private_seg_size"],
+                      "lds_bytes": meta["lds_bytes"],
+                      "stage_loop (product build, static: both sides of every branch)": loops,
+                      "behind_the_last_mfma (product build, both epilogue variants together)": whole,
+                      "epilogue_by_phase (diagnostics build, cut at its stamps)": phases}, indent=1))
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "--wino4":
+    wino4_census(sys.argv[2:])
+    sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "--loops":
     loops_census(sys.argv[2:])
     sys.exit(0)
