@@ -16,6 +16,8 @@ from .evaluate import root_traits as split_root_traits  # noqa: F401  (``root_tr
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)
+from .spectral import (SpectralProjection, SpectralStats, band_statistics, class_spectra, gram_reference, merge_statistics,  # noqa: F401
+                       moments_reference, pca_basis, project_reference)
 from .tta import TTA, VIEW_NAMES, apply_view, invert_view, tta_merge_reference  # noqa: F401
 from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss, FocalLoss, forward_loss, FusedAdam, FusedSGD,  # noqa: F401
                       PRCurve, SegConfusion, SegCounts, SegLoss, SegmentationModel, TverskyLoss, argmax_classes, average_precision,

@@ -830,6 +830,45 @@ int hpri_thin(const void* pred, int pred_kind, float threshold, int is_logits, i
               unsigned char* map, unsigned char* other, int* deleted, hipStream_t stream);
 int hpri_skeleton_links(const unsigned char* skeleton, int N, int h, int w, int* links, hipStream_t stream);
 
+/* ---- spectral statistics and projection (spectral.hip; hyperpri_amd/spectral.py) ---------------------------------------------
+ * The band axis of the cube cache.  cache, cache_dtype, slots, Hs, Ws, cs: the slots as hpri_cube_gather reads them ((slots, Hs,
+ * Ws, cs) fp32 / fp16, cs % 8 == 0 and cs <= hpri_band_max_cs, zeros above the bands); masks: (slots, Hs, Ws) uint8 (may be null
+ * with select 0).  slot_table: n int32 on the device, the slots to read (clamped into the cache by the kernels).  select 0: every
+ * pixel, 1: mask != 0, 2: mask == 0; a pixel that is not selected contributes exact zeros.
+ *   hpri_band_moments   *count (int64) = the selected pixels, sums[c] (fp64, cs) = their sum of x[c].  With pivot (fp32, cs, zero pad
+ *                       entries) and sumsq both given: sums[c] = sum of d[c] and sumsq[c] = sum of d[c]^2, d = x - pivot rounded once
+ *                       to fp32.  One pass, 16-byte loads.
+ *   hpri_band_gram      gram[i*cs + j] (fp64, cs x cs, the full symmetric matrix) = sum over the selected pixels of d[i] * d[j].
+ *                       Products and sums on v_mfma_f32_32x32x2_f32 (bitwise an fmaf chain over the pixels); the upper triangle of
+ *                       32 x 32 blocks is computed, the rest mirrored: exactly symmetric, pad rows and columns exactly zero.
+ *   Both: a sum stays in fp32 for at most hpri_band_fp32_run pixels (one RUN: run r of list entry e covers its pixels [r * RUN,
+ *   (r + 1) * RUN)) and is then added into an fp64 partial; partial a owns the runs a, a + PARTS, ... of the launch in that order
+ *   (PARTS a constant: 2048 for the moments, 256 for the Gram matrix), and a finishing kernel adds the partials in ascending order.
+ *   No floating-point atomic: two calls on the same arguments give the same bits on any gfx950 part.  workspace: at least
+ *   hpri_band_workspace_bytes(cs) bytes, 16-byte aligned -- a function of cs alone (0 for a cs the family does not take).
+ *   hpri_band_project   y[p*ks + k] = fmaf(W[k][cs-1], x[p][cs-1], ... fmaf(W[k][0], x[p][0], b[k])) for the `pixels` rows of a
+ *                       zero-padded channels-last fp32 batch x (pixels, cs); ks = roundup(K, 8), weight (ks, cs) and bias (ks) fp32
+ *                       with zero pad rows, columns and entries, so the pad channels of y are exact zeros.  v_mfma_f32_16x16x4_f32;
+ *                       the weights stay in LDS for a workgroup's lifetime, 16-byte accesses both ways.  K <= hpri_band_project_max_k
+ *                       (64); weights plus a 64-pixel tile must fit the LDS (cs <= 304 at ks = 64).
+ *   hpri_band_affine    y[p*cs + c] = fmaf(x[p*cs + c], scale[c], shift[c]) for c < C, 0 for C <= c < cs.
+ * Argument errors (a null pointer, a size <= 0, cs % 8 != 0 or beyond hpri_band_max_cs, a select or dtype out of range, a selection
+ * without masks, K beyond the maximum, a workspace that is too small, a misaligned pointer) return -1 before any launch. */
+int hpri_band_fp32_run(void);
+int hpri_band_max_cs(void);
+int hpri_band_project_max_k(void);
+size_t hpri_band_workspace_bytes(int cs);
+int hpri_band_moments(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const unsigned char* masks,
+                      const int* slot_table, int n, int select, const float* pivot, void* workspace, size_t workspace_bytes,
+                      long long* count, double* sums, double* sumsq, hipStream_t stream);
+int hpri_band_gram(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const unsigned char* masks,
+                   const int* slot_table, int n, int select, const float* pivot, void* workspace, size_t workspace_bytes,
+                   double* gram, hipStream_t stream);
+int hpri_band_project(const float* x, long long pixels, int cs, const float* weight, const float* bias, int K, float* y,
+                      hipStream_t stream);
+int hpri_band_affine(const float* x, long long pixels, int cs, int C, const float* scale, const float* shift, float* y,
+                     hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
