@@ -318,9 +318,120 @@ def root_traits(pred: torch.Tensor, threshold: Optional[float] = None, is_logits
     return out
 
 
+def centerline_counts(pred: torch.Tensor, threshold: Optional[float], truth: torch.Tensor, is_logits: bool = True) -> np.ndarray:
+    """The integers of the hard clDice: host int64 (N, 4) = per image ``|skel(P)|``, ``|skel(P) & T|``, ``|skel(T)|``,
+    ``|skel(T) & P|`` with ``skel`` the Zhang-Suen ``skeletonize``, ``P`` the decision of ``pred`` (as ``label_components`` takes it)
+    and ``T`` the truth (a device map of the same shape, fp32 read as ``int(mask) != 0`` or uint8 / bool).  Decisions, thinning and
+    counting (``hpri_centerline_counts``) run on the device; four integers per image come to the host."""
+    x, kind, thr = _decision_input(pred, threshold, "centerline_counts")
+    t, tkind = _truth_input(truth, "centerline_counts")
+    if t.shape != x.shape:
+        raise ValueError(f"centerline_counts: truth {tuple(truth.shape)} does not match the prediction {tuple(pred.shape)}")
+    N, h, w = (int(s) for s in x.shape)
+    with torch.cuda.device(x.device):
+        dp, dt = _decide(x, kind, thr, is_logits), _decide(t, tkind, 0.0, False)
+        sp, st = _thin(dp)[0], _thin(dt)[0]
+        counts = torch.zeros((N, 4), dtype=torch.int32, device=x.device)
+        _lib.call("hpri_centerline_counts", _p(sp), _p(st), _p(dp), _p(dt), N, h * w, _p(counts), _stream())
+        return np.asarray(counts.tolist(), dtype=np.int64).reshape(N, 4)
+
+
+def centerline_from_counts(counts) -> Dict[str, object]:
+    """The hard clDice of ``centerline_counts``' integers (host, fp64): ``counts`` (N, 4) or (4,).  Per row ``tprec = |skel(P) & T| /
+    |skel(P)|``, ``tsens = |skel(T) & P| / |skel(T)|`` and ``cldice = 2 tprec tsens / (tprec + tsens)``; NaN on a zero denominator,
+    as the pixel metrics.  ``pooled``: the same three from the column sums."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1, 4)
+
+    def ratios(sp, spt, st, stp):
+        nan = float("nan")
+        tp = spt / sp if sp else nan
+        ts = stp / st if st else nan
+        return tp, ts, (2 * tp * ts / (tp + ts) if tp + ts > 0 else nan)
+    rows = [ratios(*(int(v) for v in r)) for r in c]
+    pooled = ratios(*(int(v) for v in c.sum(axis=0)))
+    return {"tprec": np.array([r[0] for r in rows]), "tsens": np.array([r[1] for r in rows]), "cldice": np.array([r[2] for r in rows]),
+            "pooled": {"tprec": pooled[0], "tsens": pooled[1], "cldice": pooled[2]}, "counts": c}
+
+
+def centerline_metrics(pred: torch.Tensor, threshold: Optional[float], truth: torch.Tensor, is_logits: bool = True) -> Dict[str, object]:
+    """``centerline_from_counts(centerline_counts(...))``: the hard clDice of a prediction against a truth, per image and pooled."""
+    return centerline_from_counts(centerline_counts(pred, threshold, truth, is_logits))
+
+
 # ---------------------------------------------------------------------------------------------------
 # The contract restated in numpy (no scipy): the oracles of the GPU tests
 # ---------------------------------------------------------------------------------------------------
+_SK_PLUS = ((-1, 0), (0, -1), (0, 0), (0, 1), (1, 0))                       # E's scan order: N, W, C, E, S
+_SK_WINDOW = tuple((dy, dx) for dy in (-1, 0, 1) for dx in (-1, 0, 1))      # D's: the 3x3 window row by row
+
+
+def _sk_stack(a: np.ndarray, offsets, fill: float) -> np.ndarray:
+    """(K, N, h, w): a[n, y + dy, x + dx] for each offset, ``fill`` outside the image."""
+    N, h, w = a.shape
+    p = np.pad(a, ((0, 0), (1, 1), (1, 1)), constant_values=fill)
+    return np.stack([p[:, 1 + dy:1 + dy + h, 1 + dx:1 + dx + w] for dy, dx in offsets])
+
+
+def _sk_route(g: np.ndarray, choice: np.ndarray, offsets) -> np.ndarray:
+    """Every pixel sends g to the neighbour ``offsets[choice]`` it selected; the sum of what arrives (the gather of the kernels)."""
+    N, h, w = g.shape
+    off = np.asarray(offsets)
+    n, y, x = np.meshgrid(np.arange(N), np.arange(h), np.arange(w), indexing="ij")
+    out = np.zeros_like(g)
+    np.add.at(out, (n, y + off[choice, 0], x + off[choice, 1]), g)
+    return out
+
+
+def soft_skeleton_reference(p, iters: int, grad=None, dtype=np.float64):
+    """``soft_skeleton`` in numpy, the gradient contract included: ``p`` (..., h, w), computed in ``dtype``::
+
+        I_0 = p,  I_{j+1} = E(I_j),  d_j = I_j - D(I_{j+1}),  t_j = d_j - S_{j-1} * d_j,  S_0 = relu(d_0),  S_j = S_{j-1} + relu(t_j)
+
+    ``E``: the minimum over the in-image part of the plus neighbourhood, ``D``: the maximum over the in-image 3x3 (for float32 ``t_j``
+    is formed in fp64 and rounded once, as the kernels' fma).  Returns ``S``; with ``grad`` (the gradient wrt ``S``, p's shape) the
+    tuple ``(S, gp, A)``.  Backward, level by level from ``j = iters`` with ``gS`` (wrt ``S_j``) and ``gE`` (wrt ``I_{j+1}``)::
+
+        gd = gS * (1 - S_{j-1}) * [t_j > 0]   (j = 0: gS * [d_0 > 0]),   gS <- gS * (1 - d_j * [t_j > 0])
+        gI_j = gd + route_E(gE + route_D(-gd)),   gE <- gI_j,   gp = gI_0
+
+    with ``relu'(t) = [t > 0]`` and a min or max sending its whole gradient to its FIRST optimum in scan order (E: N, W, C, E, S; D:
+    the window row by row).  ``A`` is the same run with the absolute value of every routed term: the scale of the rounding error of
+    ``gp``."""
+    src = np.asarray(p)
+    dtype = np.dtype(dtype).type
+    a = np.ascontiguousarray(src, dtype=dtype).reshape((-1,) + src.shape[-2:])
+    iters = int(iters)
+    I, d, on, S = [a], [], [], []
+    amin, amax = [], []
+    for j in range(iters + 1):
+        e = _sk_stack(I[j], _SK_PLUS, np.inf)
+        amin.append(e.argmin(axis=0))
+        I.append(e.min(axis=0))
+        m = _sk_stack(I[j + 1], _SK_WINDOW, -np.inf)
+        amax.append(m.argmax(axis=0))
+        d.append(I[j] - m.max(axis=0))
+        if j == 0:
+            t = d[0]
+            S.append(np.maximum(t, 0))
+        else:
+            t = (d[j].astype(np.float64) - S[j - 1].astype(np.float64) * d[j].astype(np.float64)).astype(dtype)
+            S.append(S[j - 1] + np.maximum(t, 0))
+        on.append(t > 0)
+    out = S[iters].reshape(src.shape)
+    if grad is None:
+        return out
+    gS = np.ascontiguousarray(np.asarray(grad), dtype=dtype).reshape(a.shape)
+    aS = np.abs(gS)
+    gE, aE = np.zeros_like(a), np.zeros_like(a)
+    one = dtype(1)
+    for j in range(iters, -1, -1):
+        keep = one - S[j - 1] if j > 0 else np.ones_like(a)
+        gd, ad = np.where(on[j], gS * keep, 0), np.where(on[j], aS * np.abs(keep), 0)
+        fac = one - np.where(on[j], d[j], 0)
+        gS, aS = gS * fac, aS * np.abs(fac)
+        gE = gd + _sk_route(gE + _sk_route(-gd, amax[j], _SK_WINDOW), amin[j], _SK_PLUS)
+        aE = ad + _sk_route(aE + _sk_route(ad, amax[j], _SK_WINDOW), amin[j], _SK_PLUS)
+    return out, gE.reshape(src.shape), aE.reshape(src.shape)
 def boundary_reference(binary) -> np.ndarray:
     """The boundary of a (h, w) or (N, h, w) map in numpy, bool of the input's shape: foreground pixels with at least one of their
     four edge neighbours in the background or outside the image."""

@@ -757,3 +757,32 @@ def root_traits(pred: SplitPrediction, threshold: float, min_area: int = 0) -> D
             out["truth"][name].extend(t["truth"][name])
     out["names"] = list(pred.names)
     return out
+
+
+def centerline_metrics(pred: SplitPrediction, threshold: float, min_area: int = 0) -> Dict[str, object]:
+    """The hard clDice over a stored split (``distance.centerline_counts`` per group of equal-sized images): with ``P`` the decision
+    ``sigmoid(logits) > threshold`` (after ``clean_prediction(pred, threshold, min_area)`` when ``min_area > 0``), ``T`` the masks
+    (``int(mask) != 0``) and ``skel`` the Zhang-Suen ``skeletonize``
+
+    * ``tprec`` = ``|skel(P) & T| / |skel(P)|``, ``tsens`` = ``|skel(T) & P| / |skel(T)|`` and ``cldice`` = their harmonic mean,
+      pooled over the split (from the summed counts; NaN on a zero denominator, as the pixel metrics);
+    * ``per_image``: the same three as lists in the split's order, and ``counts``, the four integers of every image (``|skel(P)|``,
+      ``|skel(P) & T|``, ``|skel(T)|``, ``|skel(T) & P|``); ``names``.
+
+    Decisions, thinning and counting run on the device; four integers per image come to the host."""
+    from . import distance as D
+    _require_cuda(pred.logits, "prediction to measure")
+    _require_device(pred.masks, "evaluation mask")
+    if int(min_area) > 0:
+        pred, threshold = clean_prediction(pred, threshold, min_area, 0)[0], 0.5
+    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
+    rows = []
+    for i, j in _size_groups(pred):
+        a, b, (h, w) = pred.offsets[i], pred.offsets[j], pred.sizes[i]
+        rows.append(D.centerline_counts(pred.logits[a:b].view(j - i, h, w), float(threshold), masks[a:b].view(j - i, h, w)))
+    m = D.centerline_from_counts(np.concatenate(rows) if rows else np.zeros((0, 4), dtype=np.int64))
+    out: Dict[str, object] = dict(m["pooled"])
+    out["per_image"] = {"tprec": [float(v) for v in m["tprec"]], "tsens": [float(v) for v in m["tsens"]],
+                        "cldice": [float(v) for v in m["cldice"]], "counts": [[int(v) for v in r] for r in m["counts"]]}
+    out["names"] = list(pred.names)
+    return out

@@ -7,6 +7,7 @@ library (``csrc/step.hip``) without a host synchronisation until a value is actu
 
     crit = BCEWithLogitsLoss()                       # drop-in for nn.BCEWithLogitsLoss() (params_HyperPRI.py:60)
     crit = DiceBCELoss(pos_weight=3.0)               # or an imbalance-aware one (csrc/segloss.hip): SegLoss, DiceLoss, TverskyLoss, FocalLoss
+    crit = clDiceLoss(iters=3, base=DiceLoss())      # or with the centerline term for thin roots (csrc/skeleton.hip)
     opt  = FusedAdam(net.parameters(), lr=1e-3)      # drop-in for optim.Adam (PLTrainer.py:171-174)
     model = SegmentationModel(net, crit, optimizer="Adam", lr=1e-3)
     loss = model.training_step({"image": x, "mask": m})
@@ -291,6 +292,164 @@ class BCEWithLogitsLoss(nn.Module):
         if self._seg is not None:
             return self._seg(input, target)
         return _BCEFn.apply(input, target)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Soft skeletons and the centerline loss clDice (csrc/skeleton.hip)
+# ---------------------------------------------------------------------------------------------------
+MAX_SKELETON_ITERS = 32
+
+
+def _check_iters(iters, who: str) -> int:
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= int(iters) <= MAX_SKELETON_ITERS:
+        raise ValueError(f"{who}: iters must be an integer in [0, {MAX_SKELETON_ITERS}], got {iters!r}")
+    return int(iters)
+
+
+def _planes(t: torch.Tensor, who: str) -> Tuple[int, int, int]:
+    """(N, h, w) of a (N, ..., h, w) tensor read as planes."""
+    if t.dtype != torch.float32:
+        raise ValueError(f"{who}: need float32, got {t.dtype}")
+    if t.dim() < 2 or t.numel() == 0:
+        raise ValueError(f"{who}: need (N, ..., h, w) planes with at least one element, got {tuple(t.shape)}")
+    h, w = int(t.shape[-2]), int(t.shape[-1])
+    return t.numel() // (h * w), h, w
+
+
+class _SoftSkeletonFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p: torch.Tensor, iters: int):
+        _require_cuda(p, "soft_skeleton input")
+        N, h, w = _planes(p, "soft_skeleton")
+        with torch.cuda.device(p.device):
+            x = _flat(p, "soft_skeleton input")
+            S = torch.empty_like(x)
+            saved, nsv = None, 0
+            if ctx.needs_input_grad[0]:
+                nsv = _lib.load().hpri_soft_skeleton_saved_floats(N, h, w, iters)
+                saved = torch.empty(nsv, dtype=torch.float32, device=x.device)
+            _lib.call("hpri_soft_skeleton_fwd", _p(x), N, h, w, iters, _p(S), None if saved is None else _p(saved), nsv, _stream())
+            if saved is not None:
+                ctx.save_for_backward(x, saved)
+            ctx.geom = (N, h, w, iters)
+        return S
+
+    @staticmethod
+    def backward(ctx, gS: torch.Tensor):
+        x, saved = ctx.saved_tensors
+        N, h, w, iters = ctx.geom
+        with torch.cuda.device(x.device):
+            g = gS.contiguous().to(torch.float32)
+            nws = _lib.load().hpri_soft_skeleton_workspace_floats(N, h, w)
+            ws = torch.empty(nws, dtype=torch.float32, device=x.device)
+            gp = torch.empty_like(x)
+            _lib.call("hpri_soft_skeleton_bwd", _p(x), _p(saved), saved.numel(), _p(g), N, h, w, iters, _p(gp), _p(ws), nws, _stream())
+        return gp, None
+
+
+def soft_skeleton(p: torch.Tensor, iters: int) -> torch.Tensor:
+    """The soft skeleton of clDice (Shit et al., CVPR 2021) of fp32 device planes ``p`` (N, ..., h, w) with values in [0, 1]::
+
+        I_0 = p,  I_{j+1} = E(I_j),  d_j = I_j - D(I_{j+1}),  S_0 = relu(d_0),  S_j = S_{j-1} + relu(d_j - S_{j-1} * d_j),  j <= iters
+
+    ``E``: the minimum over the plus neighbourhood, ``D``: the maximum over the 3x3 neighbourhood, both over their in-image part
+    (``soft_erode`` / ``soft_dilate`` of the published code).  One launch forward for all levels, ``iters + 1`` launches backward;
+    a min or a max sends its gradient to its first optimum in scan order (``soft_skeleton_reference`` restates the rule), gathered
+    without atomics: bit-reproducible.  With a gradient the forward keeps ``2 * iters + 1`` planes of ``p``'s size."""
+    return _SoftSkeletonFn.apply(p, _check_iters(iters, "soft_skeleton"))
+
+
+class _clDiceFn(torch.autograd.Function):
+    """cfg = (iters, smooth, per_image, weight, base_weight).  Returns (loss, terms) with loss = weight * cl + base_weight * base_loss
+    (``base_loss``: a device scalar or None); terms = (cl, tprec, tsens) carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, pred: torch.Tensor, target: torch.Tensor, base_loss: Optional[torch.Tensor], cfg: tuple):
+        _require_cuda(pred, "clDiceLoss input")
+        with torch.cuda.device(pred.device):
+            if target.dtype != torch.float32:
+                target = target.to(torch.float32)
+            x, y = _flat(pred, "clDiceLoss input"), _flat(target, "clDiceLoss target")
+            if x.shape != y.shape:
+                raise ValueError(f"Target size ({tuple(y.shape)}) must be the same as input size ({tuple(x.shape)})")
+            N, h, w = _planes(x, "clDiceLoss")
+            iters, smooth, per_image, weight, base_weight = cfg
+            lib = _lib.load()
+            nsv, nws = lib.hpri_soft_skeleton_saved_floats(N, h, w, iters), lib.hpri_cldice_workspace_doubles(N, h, w)
+            nst = lib.hpri_cldice_state_doubles(N, int(per_image))
+            saved = torch.empty(nsv, dtype=torch.float32, device=x.device)
+            p, Sy = torch.empty_like(x), torch.empty_like(x)
+            ws = torch.empty(nws, dtype=torch.float64, device=x.device)
+            state = torch.empty(nst, dtype=torch.float64, device=x.device)
+            loss = torch.empty((), dtype=torch.float32, device=x.device)
+            terms = torch.empty(3, dtype=torch.float32, device=x.device)
+            base = None if base_loss is None else base_loss.detach().to(torch.float32).contiguous()
+            _lib.call("hpri_cldice_fwd", _p(x), _p(y), N, h, w, iters, smooth, int(per_image), weight, None if base is None else _p(base),
+                      base_weight, _p(p), None, _p(Sy), _p(saved), nsv, _p(loss), _p(terms), _p(state), nst, _p(ws), nws, _stream())
+            ctx.save_for_backward(x, y, p, Sy, saved, state)
+            ctx.cfg, ctx.geom, ctx.shape, ctx.has_base = cfg, (N, h, w), pred.shape, base_loss is not None
+            ctx.mark_non_differentiable(terms)
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, gout: torch.Tensor, _gterms=None):
+        x, y, p, Sy, saved, state = ctx.saved_tensors
+        iters, _, per_image, _, base_weight = ctx.cfg
+        N, h, w = ctx.geom
+        with torch.cuda.device(x.device):
+            g = gout.contiguous().to(torch.float32)
+            nws = _lib.load().hpri_soft_skeleton_workspace_floats(N, h, w)
+            ws = torch.empty(nws, dtype=torch.float32, device=x.device)
+            dx = torch.empty_like(x)
+            gbase = torch.empty((), dtype=torch.float32, device=x.device) if ctx.has_base else None
+            _lib.call("hpri_cldice_bwd", _p(x), _p(y), _p(p), _p(Sy), _p(saved), saved.numel(), N, h, w, iters, int(per_image), _p(state),
+                      state.numel(), _p(g), base_weight, None if gbase is None else _p(gbase), _p(dx), _p(ws), nws, _stream())
+        return dx.view(ctx.shape), None, gbase, None
+
+
+class clDiceLoss(nn.Module):
+    """``(1 - alpha) * base(x, y) + alpha * cl(x, y)`` over fp32 logits ``x`` (N, ..., h, w) and a target of the same shape, with the
+    centerline term of clDice (Shit et al., CVPR 2021; ``csrc/skeleton.hip``)::
+
+        Sp = soft_skeleton(sigmoid(x), iters),  Sy = soft_skeleton(y, iters)          (no gradient into y)
+        tprec = (sum Sp*y + smooth) / (sum Sp + smooth),  tsens = (sum Sy*p + smooth) / (sum Sy + smooth)
+        cl = mean over groups of 1 - 2 * tprec * tsens / (tprec + tsens)
+
+    A group is one plane (``per_image=True``) or the whole batch.  ``base``: a ``SegLoss`` (any of its family) or a
+    ``BCEWithLogitsLoss``; default ``DiceLoss(smooth, per_image)``.  It runs through its own path untouched; the weighted sum is
+    formed inside the centerline term's finalize kernel and the base's upstream gradient inside its last backward launch, so no
+    other kernel than the two losses' own is launched (autograd adds their two logit gradients).  ``alpha = 0`` is ``base`` alone, bit
+    for bit, without any skeleton launch; ``alpha = 1`` does not evaluate ``base``.  Forward: one launch for both skeletons and the
+    sums plus a finalize; backward: ``iters + 1`` launches; fp64 sums in a fixed order, gathers instead of atomics: bit-reproducible,
+    no host synchronisation.  The forward keeps ``2 * iters + 3`` planes of the logits' size for the backward.  The module sits
+    outside the network's tape, like ``SegLoss``, so it works in every precision mode.  A ratio whose denominator is 0 (``smooth = 0``
+    and an empty skeleton) counts as 0; ``tprec + tsens == 0`` gives ``cl = 1`` with a zero gradient.  ``last_terms``: the last
+    call's ``cl``, mean ``tprec`` and mean ``tsens`` as a 3-element device tensor."""
+
+    def __init__(self, iters: int = 3, alpha: float = 0.5, smooth: float = 1.0, base: Optional[nn.Module] = None, per_image: bool = False):
+        super().__init__()
+        self.iters = _check_iters(iters, "clDiceLoss")
+        self.alpha, self.smooth, self.per_image = float(alpha), float(smooth), bool(per_image)
+        if not 0 <= self.alpha <= 1:
+            raise ValueError(f"clDiceLoss: alpha must lie in [0, 1], got {self.alpha}")
+        if not self.smooth >= 0:
+            raise ValueError(f"clDiceLoss: smooth must not be negative, got {self.smooth}")
+        if base is None:
+            base = DiceLoss(self.smooth, self.per_image)
+        if not isinstance(base, (SegLoss, BCEWithLogitsLoss)):
+            raise TypeError(f"clDiceLoss: base must be a SegLoss or a BCEWithLogitsLoss, got {type(base).__name__}")
+        self.base = base
+        self.last_terms: Optional[torch.Tensor] = None
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:   # noqa: A002 (torch's names)
+        if self.alpha == 0:
+            return self.base(input, target)
+        base_loss = None if self.alpha == 1 else self.base(input, target)
+        loss, self.last_terms = _clDiceFn.apply(input, target, base_loss, (self.iters, self.smooth, self.per_image, self.alpha, 1.0 - self.alpha))
+        return loss
+
+    def extra_repr(self) -> str:
+        return ", ".join(f"{k}={getattr(self, k)}" for k in ("iters", "alpha", "smooth", "per_image"))
 
 
 def _takes_fused_head(criterion: nn.Module) -> bool:

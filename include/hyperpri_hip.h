@@ -869,6 +869,54 @@ int hpri_band_project(const float* x, long long pixels, int cs, const float* wei
 int hpri_band_affine(const float* x, long long pixels, int cs, int C, const float* scale, const float* shift, float* y,
                      hipStream_t stream);
 
+/* ---- soft skeletons and the centerline loss clDice (skeleton.hip; hyperpri_amd/trainer.py, distance.py) ------------------------
+ * fp32 planes (N, h, w), contiguous, values meant to lie in [0, 1]; 0 <= iters <= hpri_soft_skeleton_max_iters (32).
+ *   E(I)[u] = min over the in-image part of the plus neighbourhood {N, W, C, E, S} of u,  D(I)[u] = max over the in-image 3x3
+ *   I_0 = p,  I_{j+1} = E(I_j),  d_j = I_j - D(I_{j+1}),  S_0 = relu(d_0),  S_j = S_{j-1} + relu(fma(-S_{j-1}, d_j, d_j))
+ *   hpri_soft_skeleton_fwd  S = S_iters in ONE launch (tiles of hpri_soft_skeleton_tile pixels a side with a halo of iters + 2 in
+ *                           LDS: hpri_soft_skeleton_lds_bytes(iters)).  saved != NULL: also I_1 .. I_{iters+1} and S_0 ..
+ *                           S_{iters-1}, hpri_soft_skeleton_saved_floats = (2 iters + 1) N h w floats, for the backward.
+ *   hpri_soft_skeleton_bwd  grad_p from grad_S, one launch per level j = iters .. 0:  gd = gS (1 - S_{j-1}) [t_j > 0],
+ *                           gS <- gS (1 - d_j [t_j > 0]),  gI_j = gd + route_E(gE + route_D(-gd)),  gE <- gI_j.  A min or a max
+ *                           sends its gradient to its FIRST optimum in scan order (E: N, W, C, E, S; D: the window row by row);
+ *                           the routes are gathers summed in a fixed order in fp64: no floating-point atomic, bit-reproducible,
+ *                           independent of the tiling.  workspace: hpri_soft_skeleton_workspace_floats = 4 N h w floats.
+ *   hpri_cldice_fwd         Sp = soft_skeleton(sigmoid(logits)) and Sy = soft_skeleton(target) in one launch (p = sigmoid(logits)
+ *                           written once; Sp may be NULL), with per group (an image with per_image, else the batch)
+ *                           tprec = (sum Sp y + s) / (sum Sp + s), tsens = (sum Sy p + s) / (sum Sy + s), cl = 1 - 2 tprec tsens /
+ *                           (tprec + tsens) from fp64 partial sums per workgroup in a fixed order and a one-workgroup finalize:
+ *                           loss[0] = weight * mean_g cl_g (+ base_weight * base_loss[0] with base_loss != NULL, a device scalar);
+ *                           terms[0..2] = mean cl, mean tprec, mean tsens; state: 3 doubles per group (a, b, c below).  A ratio
+ *                           with a zero denominator is 0; tprec + tsens == 0 gives cl = 1 and zero coefficients.
+ *   hpri_cldice_bwd         dlogits = grad_out * (skeleton-backward(a_g y + b_g) + c_g Sy) * sigmoid(x) * sigmoid(-x) in iters + 1
+ *                           launches, no host round trip; grad_out: device scalar, NULL = 1; grad_base != NULL: grad_base[0] =
+ *                           grad_out * base_weight.
+ *   hpri_centerline_counts  counts[4n .. 4n+3] += |skel(P)|, |skel(P) & T|, |skel(T)|, |skel(T) & P| of image n over uint8 maps
+ *                           (non-zero = set).  ACCUMULATED.
+ * The size functions are pure host functions.  Argument errors (a null pointer, a size <= 0, N > 32767, a side > 2^30, N*h*w >= 2^31, iters
+ * outside [0, 32], smooth < 0, a buffer that is too small) return -1 before any launch. */
+int hpri_soft_skeleton_tile(void);
+int hpri_soft_skeleton_max_iters(void);
+size_t hpri_soft_skeleton_lds_bytes(int iters);
+size_t hpri_soft_skeleton_saved_floats(int N, int h, int w, int iters);
+size_t hpri_soft_skeleton_workspace_floats(int N, int h, int w);
+size_t hpri_cldice_workspace_doubles(int N, int h, int w);
+size_t hpri_cldice_state_doubles(int N, int per_image);
+int hpri_soft_skeleton_fwd(const float* p, int N, int h, int w, int iters, float* S, float* saved, size_t saved_floats,
+                           hipStream_t stream);
+int hpri_soft_skeleton_bwd(const float* p, const float* saved, size_t saved_floats, const float* grad_S, int N, int h, int w,
+                           int iters, float* grad_p, float* workspace, size_t ws_floats, hipStream_t stream);
+int hpri_cldice_fwd(const float* logits, const float* target, int N, int h, int w, int iters, float smooth, int per_image,
+                    float weight, const float* base_loss, float base_weight, float* p, float* Sp, float* Sy, float* saved,
+                    size_t saved_floats, float* loss, float* terms, double* state, size_t state_doubles, double* workspace,
+                    size_t ws_doubles, hipStream_t stream);
+int hpri_cldice_bwd(const float* logits, const float* target, const float* p, const float* Sy, const float* saved,
+                    size_t saved_floats, int N, int h, int w, int iters, int per_image, const double* state, size_t state_doubles,
+                    const float* grad_out, float base_weight, float* grad_base, float* dlogits, float* workspace, size_t ws_floats,
+                    hipStream_t stream);
+int hpri_centerline_counts(const unsigned char* skel_pred, const unsigned char* skel_truth, const unsigned char* pred,
+                           const unsigned char* truth, int N, long long per_image, int* counts, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,7 @@ HOT = (
     "bn_", "col_", "maxpool2", "nchw_to_nhwc", "outconv", "bce_", "adam", "copy_slice", "fill_pad", "to_planes",
     "cube_gather_kernel", "mask_gather_kernel", "cube_warp_kernel", "mask_warp_kernel", "cube_deform_kernel", "mask_deform_kernel", "elastic_field_kernel", "seg_loss_", "tta_merge_",
     "band_moments_kernel", "band_gram_kernel", "band_project_kernel", "band_affine_kernel",
+    "soft_skel_fwd_kernel", "soft_skel_bwd_kernel", "cldice_finalize_kernel", "centerline_count_kernel",
 )
 
 # conv_fwd_kernel<KS, 2, 2, ...> (fp32 direct kernel at three workgroups per CU = 168 registers; it needs 170 for a few
