@@ -131,7 +131,7 @@ extern "C" int hpri_cube_gather(const void* cache, int cache_dtype, int slots, i
   CACHE_REQUIRE(p.who, cache && table && dst, "null pointer");
   const CacheSlots c = {cache_dtype, cs, cs};
   if (int e = cache_check(p, &c)) return e;
-  CACHE_REQUIRE(p.who, cache_aligned16(cache, dst, table), "buffers must be 16-byte aligned");
+  CACHE_REQUIRE(p.who, hpri_aligned16(cache, dst, table), "buffers must be 16-byte aligned");
   const int q = cs / 4;
   const dim3 grid = cache_grid(cache_row_items(p, q, GATHER_ITEM), 8);  // eight workgroups per CU, grid-stride over the rest
   if (cache_dtype == 0)
@@ -164,7 +164,7 @@ extern "C" int hpri_mask_gather(const unsigned char* masks, int slots, int Hs, i
   const CachePass p = {"mask_gather", slots, Hs, Ws, N, h, w, true};
   CACHE_REQUIRE(p.who, masks && table && dst, "null pointer");
   if (int e = cache_check(p)) return e;
-  CACHE_REQUIRE(p.who, cache_aligned16(table), "the table must be 16-byte aligned");
+  CACHE_REQUIRE(p.who, hpri_aligned16(table), "the table must be 16-byte aligned");
   hipLaunchKernelGGL(mask_gather_kernel, cache_grid(cache_pixel_blocks(p), 8), dim3(256), 0, stream, masks, slots, Hs, Ws, table, N, h, w,
                      dst);
   HPRI_CHECK_LAUNCH();

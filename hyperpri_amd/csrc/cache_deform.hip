@@ -67,7 +67,7 @@ extern "C" int hpri_elastic_field(const float* nodes, long long nodes_len, const
   CACHE_REQUIRE(p.who, deform && field && (nodes || nodes_len == 0), "null pointer");
   if (int e = cache_check(p)) return e;
   // (the node table is read as (dx, dy) pairs: 8 bytes)
-  CACHE_REQUIRE(p.who, cache_aligned16(deform, field) && ((uintptr_t)nodes & 7) == 0, "buffers must be 16-byte aligned (the node table: 8)");
+  CACHE_REQUIRE(p.who, hpri_aligned16(deform, field) && ((uintptr_t)nodes & 7) == 0, "buffers must be 16-byte aligned (the node table: 8)");
   hipLaunchKernelGGL(elastic_field_kernel, cache_grid(cache_pixel_blocks(p), 8), dim3(256), 0, stream, nodes, nodes_len, deform, N, h, w,
                      field);
   HPRI_CHECK_LAUNCH();

@@ -2,7 +2,7 @@
 // their grids: every rule once.  A failed requirement is reported as "<entry>: <rule>", in the order the checks are written.
 #pragma once
 #include <stdio.h>
-#include "common.h"
+#include "tail_helpers.h"            // hpri_aligned16, hpri_grid_per_cu
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
@@ -34,13 +34,8 @@ static inline int cache_check(const CachePass& p, const CacheSlots* c = nullptr)
   return HPRI_OK;
 }
 
-template <typename... P> static inline bool cache_aligned16(P... ptr) { return ((((uintptr_t)ptr) | ...) & 15) == 0; }
-
-// blocks = min(items, per_cu x CUs): the kernels stride over the rest
-static inline dim3 cache_grid(long long items, int per_cu) {
-  const long long cap = (long long)per_cu * hpri_cu_count();
-  return dim3((unsigned)(items < cap ? items : cap));
-}
+// blocks = min(items, per_cu x CUs): the kernels stride over the rest (items >= 1 after cache_check and the launchers' own checks)
+static inline dim3 cache_grid(long long items, int per_cu) { return dim3(hpri_grid_per_cu(items, 1, per_cu)); }
 // work items of `item` consecutive channel quads of one window row / workgroups of 256 pixels
 static inline long long cache_row_items(const CachePass& p, int q, int item) { return (long long)p.N * p.h * (((long long)p.w * q + item - 1) / item); }
 static inline long long cache_pixel_blocks(const CachePass& p) { return ((long long)p.N * p.h * p.w + 255) / 256; }

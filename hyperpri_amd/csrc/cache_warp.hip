@@ -280,7 +280,7 @@ static int cube_resample_launch(const CachePass& p, bool deformed, const void* c
   CACHE_REQUIRE(p.who, cache && entries && dst && (deform || !deformed), "null pointer");
   const CacheSlots c = {cache_dtype, cs, C};
   if (int e = cache_check(p, &c)) return e;
-  CACHE_REQUIRE(p.who, cache_aligned16(cache, dst, entries, deform, field), "buffers must be 16-byte aligned");
+  CACHE_REQUIRE(p.who, hpri_aligned16(cache, dst, entries, deform, field), "buffers must be 16-byte aligned");
   const int q = cs / 4;
   const dim3 grid = cache_grid(cache_row_items(p, q, WARP_ITEM), deformed ? 6 : 8), block(WARP_THREADS);
   const float* c32 = (const float*)cache;
@@ -361,7 +361,7 @@ static int mask_resample_launch(const CachePass& p, bool deformed, const unsigne
                                 const float* field, float* dst, hipStream_t stream) {
   CACHE_REQUIRE(p.who, masks && entries && dst && (deform || !deformed), "null pointer");
   if (int e = cache_check(p)) return e;
-  CACHE_REQUIRE(p.who, cache_aligned16(entries, deform, field),
+  CACHE_REQUIRE(p.who, hpri_aligned16(entries, deform, field),
                 deformed ? "the entries and the field must be 16-byte aligned" : "the entries must be 16-byte aligned");
   const dim3 grid = cache_grid(cache_pixel_blocks(p), 8), block(256);
   if (!deformed) hipLaunchKernelGGL(mask_warp_kernel, grid, block, 0, stream, masks, p.slots, p.Hs, p.Ws, entries, p.N, p.h, p.w, dst);

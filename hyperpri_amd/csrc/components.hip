@@ -39,6 +39,7 @@
 // area <= max_hole becomes foreground.  Holes are found in the INPUT decision, not after speck removal: the two edits act on
 // disjoint pixels (one on foreground, one on background pixels of the input), so their order is immaterial.
 #include "decision.h"                    // CcDecision, cc_decide (shared with distance.hip)
+#include "tail_helpers.h"
 
 #define CC_THREADS 256
 #define CC_TILE_H 32
@@ -182,11 +183,6 @@ __global__ __launch_bounds__(CC_THREADS) void cc_border_kernel(const CcMode m, i
 }
 
 // ---- flatten, out of place; one wave per row, which also counts the row's roots -------------------------------------------------
-__device__ __forceinline__ int cc_wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int rows, int w, const int* __restrict__ parent,
                                                                 int* __restrict__ root, int* __restrict__ rowcount) {
   const int lane = threadIdx.x & 63, waves = CC_THREADS / 64;
@@ -204,7 +200,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_flatten_kernel(int rows, int w,
       }
       root[i] = p;
     }
-    cnt = cc_wave_sum(cnt);
+    cnt = hpri_wave_sum(cnt);
     if (lane == 0 && rowcount) rowcount[r] = cnt;
   }
 }
@@ -301,28 +297,19 @@ struct CcCleanArgs {
 };
 
 __global__ __launch_bounds__(CC_THREADS) void cc_clean_kernel(const CcCleanArgs a) {
-  __shared__ unsigned int red[4];
-  if (threadIdx.x < 4) red[threadIdx.x] = 0;
-  __syncthreads();
-  unsigned int c[4] = {0, 0, 0, 0};
-  for (long long it = (long long)blockIdx.x * CC_THREADS + threadIdx.x; it < a.n_pix; it += (long long)gridDim.x * CC_THREADS) {
-    const int i = (int)it, r = a.root[i], ar = a.area[r];
-    int fg = a.dec[i];
-    if (fg) {
-      if (ar < a.min_area) { fg = 0; c[1] += 1; c[0] += r == i; }
-    } else if (a.edge[r] == 0 && ar <= a.max_hole) {
-      fg = 1; c[3] += 1; c[2] += r == i;
+  hpri_block_count4(a.stats, [&](unsigned int (&c)[4]) {
+    for (long long it = (long long)blockIdx.x * CC_THREADS + threadIdx.x; it < a.n_pix; it += (long long)gridDim.x * CC_THREADS) {
+      const int i = (int)it, r = a.root[i], ar = a.area[r];
+      int fg = a.dec[i];
+      if (fg) {
+        if (ar < a.min_area) { fg = 0; c[1] += 1; c[0] += r == i; }
+      } else if (a.edge[r] == 0 && ar <= a.max_hole) {
+        fg = 1; c[3] += 1; c[2] += r == i;
+      }
+      a.out[i] = (unsigned char)fg;
+      if (a.out_logits) a.out_logits[i] = fg ? a.logit : -a.logit;
     }
-    a.out[i] = (unsigned char)fg;
-    if (a.out_logits) a.out_logits[i] = fg ? a.logit : -a.logit;
-  }
-  for (int k = 0; k < 4; ++k) {
-    unsigned int v = c[k];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&red[k], v);
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && red[threadIdx.x]) atomicAdd(&a.stats[threadIdx.x], (unsigned long long)red[threadIdx.x]);
+  });
 }
 
 // ---- measuring ------------------------------------------------------------------------------------------------------------------
@@ -377,13 +364,7 @@ __global__ __launch_bounds__(CC_THREADS) void cc_measure_kernel(int rows, int h,
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-static inline unsigned cc_grid(long long items, int per_block) {
-  long long blocks = (items + per_block - 1) / per_block;
-  const long long cap = 8LL * hpri_cu_count();                         // eight workgroups per CU, grid-stride over the rest (as segmap.hip)
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
+static inline int cc_grid(long long items, int per_block) { return hpri_grid_per_cu(items, per_block, 8); }      // eight workgroups per CU
 
 static inline long long cc_dec_ints(long long n) { return (n + 3) / 4; }
 

@@ -31,6 +31,7 @@
 // Links of a skeleton, per image: S pixels; E4 pairs of horizontally or vertically adjacent pixels; Ed pairs of diagonally adjacent
 // pixels whose two common edge neighbours are both off the skeleton (so a corner is not counted twice).
 #include "decision.h"
+#include "tail_helpers.h"
 
 #define DT_THREADS 256
 #define DT_MAX_W 8192                    // the row of g^2 in LDS: 32 KB
@@ -108,7 +109,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_select_stats_kernel(const int* 
     if (p < per && dt_selected(sel, sel_kind, n * per + p)) v = values[n * per + p];
     const int cnt = __popcll(__ballot(v >= 0));
     if (cnt == 0) continue;                                            // (uniform per wave)
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+    v = hpri_wave_max(v);
     if (lane == 0) {
       atomicAdd(&stats[(long long)n * stride], cnt);
       atomicMax(&stats[(long long)n * stride + 1], v);
@@ -185,11 +186,6 @@ __global__ __launch_bounds__(DT_THREADS) void dt_thin_kernel(const unsigned char
   }
 }
 
-__device__ __forceinline__ int dt_wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 __global__ __launch_bounds__(DT_THREADS) void dt_links_kernel(const unsigned char* __restrict__ skel, int N, int h, int w, int* links) {
   const int lane = threadIdx.x & 63, waves = DT_THREADS / 64, per = h * w, chunks = (per + 63) / 64;
   const long long items = dt_wave_items(N, per);
@@ -207,7 +203,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_links_kernel(const unsigned cha
       }
     }
     if (__ballot(s != 0) == 0) continue;                               // (uniform per wave)
-    s = dt_wave_sum(s); e4 = dt_wave_sum(e4); ed = dt_wave_sum(ed);
+    s = hpri_wave_sum(s); e4 = hpri_wave_sum(e4); ed = hpri_wave_sum(ed);
     if (lane == 0) {
       atomicAdd(&links[3 * n], s);
       if (e4) atomicAdd(&links[3 * n + 1], e4);
@@ -217,13 +213,7 @@ __global__ __launch_bounds__(DT_THREADS) void dt_links_kernel(const unsigned cha
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-static inline unsigned dt_grid(long long items, int per_block) {
-  long long blocks = (items + per_block - 1) / per_block;
-  const long long cap = 8LL * hpri_cu_count();                         // eight workgroups per CU, grid-stride over the rest (as components.hip)
-  if (blocks > cap) blocks = cap;
-  if (blocks < 1) blocks = 1;
-  return (unsigned)blocks;
-}
+static inline int dt_grid(long long items, int per_block) { return hpri_grid_per_cu(items, per_block, 8); }      // eight workgroups per CU
 
 extern "C" int hpri_edt_max_width() { return DT_MAX_W; }
 extern "C" int hpri_edt_col_threads() { return DT_THREADS; }
@@ -300,7 +290,7 @@ extern "C" int hpri_thin(const void* pred, int pred_kind, float threshold, int i
     hipLaunchKernelGGL(dt_decide_kernel, dim3(dt_grid((long long)N * h * w, DT_THREADS)), dim3(DT_THREADS), 0, stream, d, N * h * w, map);
     HPRI_CHECK_LAUNCH();
   }
-  const unsigned grid = dt_grid((long long)N * hpri_cdiv(h * w, 64), DT_THREADS / 64);
+  const int grid = dt_grid((long long)N * hpri_cdiv(h * w, 64), DT_THREADS / 64);
   for (int j = 0; j < pairs; ++j) {
     hipLaunchKernelGGL(dt_thin_kernel, dim3(grid), dim3(DT_THREADS), 0, stream, map, other, N, h, w, 0, deleted + (long long)j * N);
     HPRI_CHECK_LAUNCH();

@@ -8,7 +8,7 @@
 //
 // All kernels are HBM-bound single passes (forward 4K + 8 bytes per pixel, backward 8K + 8): a lane owns four adjacent pixels of
 // one image and walks the K planes, so a wave reads 1 KB contiguous per plane -- 16-byte accesses when HW % 4 == 0 and every base
-// pointer is 16-byte aligned (the rule of segmap.hip's quads), element accesses otherwise; which lane owns which pixel is the same
+// pointer is 16-byte aligned (hpri_load4 / hpri_store4), element accesses otherwise; which lane owns which pixel is the same
 // in both forms, so their results are bit-identical.  As in step.hip: fixed-order fp64 partial sums, integer atomics only, no
 // host synchronisation (scalars stay on the device), nothing allocated here.
 //
@@ -17,20 +17,14 @@
 // check -- the class's logit is picked by a select while the planes stream past, only the weight is read at [t].  An invalid
 // target cannot be reported without a synchronisation, so it POISONS the result instead: the loss becomes NaN (gradient rows of
 // such pixels are zero), the confusion pass counts it in counts[K*K].
-#include "common.h"
+#include "tail_helpers.h"
 
 #define MC_THREADS 256
-#define MC_MAX_BLOCKS 1024
 #define MC_MAX_K 64
 enum { MC_T_F32 = 0, MC_T_U8 = 1, MC_T_I64 = 2 };
 enum { MC_VALID = 0, MC_IGNORED = 1, MC_INVALID = 2 };
 
-static inline int mc_blocks(long long items) {
-  long long b = (items + MC_THREADS - 1) / MC_THREADS;
-  if (b > MC_MAX_BLOCKS) b = MC_MAX_BLOCKS;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+static inline int mc_blocks(long long items) { return hpri_grid_capped(items, MC_THREADS); }
 
 struct McQuad {                 // four adjacent pixels of one image
   long long plane0;             // element offset of class plane 0 at the quad's first pixel
@@ -47,31 +41,6 @@ __device__ __forceinline__ McQuad mc_quad(long long it, long long qpi, long long
   return q;
 }
 
-// lanes past cnt read nothing and hold 0
-__device__ __forceinline__ void mc_load4(const float* __restrict__ p, int cnt, int vec, float (&x)[4]) {
-  if (vec) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = v[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = j < cnt ? p[j] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void mc_store4(float* __restrict__ p, int cnt, int vec, const float (&x)[4]) {
-  if (vec) {
-    f32x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = x[j];
-    *reinterpret_cast<f32x4*>(p) = v;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) p[j] = x[j];
-  }
-}
-
 __device__ __forceinline__ void mc_classify(long long v, int K, int use_ignore, long long ignore_index, int& cls, int& state) {
   if (use_ignore && v == ignore_index) { cls = 0; state = MC_IGNORED; }
   else if (v < 0 || v >= K) { cls = 0; state = MC_INVALID; }
@@ -85,7 +54,7 @@ __device__ __forceinline__ void mc_targets(const void* __restrict__ target, int 
   bool bad[4] = {false, false, false, false};
   if (tkind == MC_T_F32) {
     float f[4];
-    mc_load4(reinterpret_cast<const float*>(target) + pix, cnt, vec, f);
+    hpri_load4(reinterpret_cast<const float*>(target) + pix, cnt, vec, f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       bad[j] = !(f[j] > -2147483648.f && f[j] < 2147483648.f);      // NaN, infinities, beyond any class index
@@ -148,7 +117,7 @@ __global__ __launch_bounds__(MC_THREADS) void softmax_ce_fwd_kernel(const float*
 #pragma unroll UNROLL
     for (int k = 0; k < K; ++k) {
       float v[4];
-      mc_load4(px + (long long)k * HW, q.cnt, vec, v);
+      hpri_load4(px + (long long)k * HW, q.cnt, vec, v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const float d = v[j] - m[j];
@@ -170,17 +139,10 @@ __global__ __launch_bounds__(MC_THREADS) void softmax_ce_fwd_kernel(const float*
         sb += 1.0;
       }
     }
-    mc_store4(lse + q.pix, q.cnt, vec, o);
+    hpri_store4(lse + q.pix, q.cnt, vec, o);
   }
-  red[0][threadIdx.x] = sl; red[1][threadIdx.x] = sw; red[2][threadIdx.x] = sb;
-  __syncthreads();
-  for (int w = MC_THREADS / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) red[r][threadIdx.x] += red[r][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+  const double s3[3] = {sl, sw, sb};
+  hpri_block_sum(red, s3);
   if (threadIdx.x < 3) partial[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0];
 }
 
@@ -190,20 +152,11 @@ __global__ __launch_bounds__(MC_THREADS) void softmax_ce_finalize_kernel(const d
                                                                          float* __restrict__ loss, float* __restrict__ denom,
                                                                          double* __restrict__ totals) {
   __shared__ double red[3][MC_THREADS];
+  double s[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += MC_THREADS) s += partial[(size_t)r * nblk + i];
-    red[r][threadIdx.x] = s;
-  }
-  __syncthreads();
-  for (int w = MC_THREADS / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) {
-#pragma unroll
-      for (int r = 0; r < 3; ++r) red[r][threadIdx.x] += red[r][threadIdx.x + w];
-    }
-    __syncthreads();
-  }
+  for (int r = 0; r < 3; ++r)
+    for (int i = threadIdx.x; i < nblk; i += MC_THREADS) s[r] += partial[(size_t)r * nblk + i];
+  hpri_block_sum(red, s);
   if (threadIdx.x == 0) {
     const double sl = red[0][0], sw = red[1][0], sb = red[2][0];
     const double l = mean ? sl / sw : sl;
@@ -235,7 +188,7 @@ __global__ __launch_bounds__(MC_THREADS) void softmax_ce_bwd_kernel(const float*
     int cls[4], state[4];
     mc_targets(target, tkind, q.pix, q.cnt, vec, K, use_ignore, ignore_index, cls, state);
     float l[4], c[4], others[4];
-    mc_load4(lse + q.pix, q.cnt, vec, l);
+    hpri_load4(lse + q.pix, q.cnt, vec, l);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       // (an ignored or invalid pixel: exact zeros, whatever g / denom is -- 0 * inf would be NaN)
@@ -249,7 +202,7 @@ __global__ __launch_bounds__(MC_THREADS) void softmax_ce_bwd_kernel(const float*
 #pragma unroll
       for (int k = 0; k < KT; ++k) {
         float v[4];
-        mc_load4(px + (long long)k * HW, q.cnt, vec, v);
+        hpri_load4(px + (long long)k * HW, q.cnt, vec, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           p[k][j] = expf(v[j] - l[j]);
@@ -261,23 +214,23 @@ __global__ __launch_bounds__(MC_THREADS) void softmax_ce_bwd_kernel(const float*
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = state[j] == MC_VALID ? (k == cls[j] ? -others[j] : p[k][j]) * c[j] : 0.f;
-        mc_store4(pd + (long long)k * HW, q.cnt, vec, o);
+        hpri_store4(pd + (long long)k * HW, q.cnt, vec, o);
       }
     } else {
 #pragma unroll 4
       for (int k = 0; k < K; ++k) {
         float v[4];
-        mc_load4(px + (long long)k * HW, q.cnt, vec, v);
+        hpri_load4(px + (long long)k * HW, q.cnt, vec, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) others[j] += k == cls[j] ? 0.f : expf(v[j] - l[j]);
       }
 #pragma unroll 4
       for (int k = 0; k < K; ++k) {
         float v[4], o[4];
-        mc_load4(px + (long long)k * HW, q.cnt, vec, v);
+        hpri_load4(px + (long long)k * HW, q.cnt, vec, v);
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = state[j] == MC_VALID ? (k == cls[j] ? -others[j] : expf(v[j] - l[j])) * c[j] : 0.f;
-        mc_store4(pd + (long long)k * HW, q.cnt, vec, o);
+        hpri_store4(pd + (long long)k * HW, q.cnt, vec, o);
       }
     }
   }
@@ -306,13 +259,13 @@ __global__ __launch_bounds__(MC_THREADS) void seg_confusion_kernel(const float* 
     float best[4];
     int arg[4];
     const float* px = x + q.plane0;
-    mc_load4(px, q.cnt, vec, best);
+    hpri_load4(px, q.cnt, vec, best);
 #pragma unroll
     for (int j = 0; j < 4; ++j) arg[j] = 0;
 #pragma unroll 4
     for (int k = 1; k < K; ++k) {
       float v[4];
-      mc_load4(px + (long long)k * HW, q.cnt, vec, v);
+      hpri_load4(px + (long long)k * HW, q.cnt, vec, v);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool take = v[j] > best[j] || (v[j] != v[j] && best[j] == best[j]);
@@ -358,8 +311,6 @@ __global__ __launch_bounds__(MC_THREADS) void seg_confusion_kernel(const float* 
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static inline bool mc_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static int mc_check(const char* who, int tkind, int N, int K, long long HW) {
   (void)who;
   HPRI_REQUIRE(K >= 2 && K <= MC_MAX_K, "multiclass: the number of classes must lie in [2, 64]");
@@ -379,7 +330,7 @@ extern "C" int hpri_softmax_ce_fwd(const float* logits, const void* target, int 
   const long long items = (long long)N * ((HW + 3) / 4);
   const int nb = mc_blocks(items);
   if (3 * (size_t)nb > ws_doubles) return hpri_set_error(HPRI_ERR_WORKSPACE, "softmax_ce_fwd: workspace too small");
-  const int vec = HW % 4 == 0 && mc_aligned16(logits) && mc_aligned16(target) && mc_aligned16(lse);
+  const int vec = HW % 4 == 0 && hpri_aligned16(logits, target, lse);
 #define MC_FWD(KT)                                                                                                              \
   hipLaunchKernelGGL(softmax_ce_fwd_kernel<KT>, dim3(nb), dim3(MC_THREADS), 0, stream, logits, target, target_kind, weight, N, K, \
                      HW, use_ignore, ignore_index, vec, lse, workspace)
@@ -398,7 +349,7 @@ extern "C" int hpri_softmax_ce_bwd(const float* logits, const float* lse, const 
   if (int rc = mc_check("softmax_ce_bwd", target_kind, N, K, HW)) return rc;
   const long long items = (long long)N * ((HW + 3) / 4);
   const int nb = mc_blocks(items);
-  const int vec = HW % 4 == 0 && mc_aligned16(logits) && mc_aligned16(target) && mc_aligned16(lse) && mc_aligned16(dlogits);
+  const int vec = HW % 4 == 0 && hpri_aligned16(logits, target, lse, dlogits);
 #define MC_BWD(KT)                                                                                                              \
   hipLaunchKernelGGL(softmax_ce_bwd_kernel<KT>, dim3(nb), dim3(MC_THREADS), 0, stream, logits, lse, target, target_kind, weight, \
                      N, K, HW, use_ignore, ignore_index, vec, denom, grad_out, dlogits)
@@ -416,7 +367,7 @@ extern "C" int hpri_seg_confusion(const float* logits, const void* target, int t
   HPRI_REQUIRE(counts || classes, "seg_confusion: null pointer (neither counts nor a class map asked for)");
   if (int rc = mc_check("seg_confusion", target ? target_kind : MC_T_F32, N, K, HW)) return rc;
   const long long items = (long long)N * ((HW + 3) / 4);
-  const int vec = HW % 4 == 0 && mc_aligned16(logits) && mc_aligned16(target) && mc_aligned16(classes);
+  const int vec = HW % 4 == 0 && hpri_aligned16(logits, target, classes);
   hipLaunchKernelGGL(seg_confusion_kernel, dim3(mc_blocks(items)), dim3(MC_THREADS), 0, stream, logits, target, target_kind, N, K, HW,
                      use_ignore, ignore_index, vec, reinterpret_cast<unsigned long long*>(counts), classes);
   HPRI_CHECK_LAUNCH();

@@ -13,14 +13,14 @@
 //
 // One pass forward (8 bytes per element), one pass backward (12), HBM-bound.  A lane owns four adjacent elements of one image:
 // 16-byte accesses when hw % 4 == 0 and every base pointer is 16-byte aligned, element accesses otherwise; which lane owns which
-// element is the same in both forms, so their results are bit-identical (the rule of multiclass.hip).  A workgroup works on one
+// element is the same in both forms, so their results are bit-identical (hpri_load4 / hpri_store4).  A workgroup works on one
 // image at a time (a "unit": one of the bpi slices of an image), so its four fp64 partial sums (pointwise, I, P, Y) belong to one
 // group; they are reduced through LDS in a fixed order, and the finalize kernel sums the units of a group in a fixed order too:
 // no floating-point atomics, bit-reproducible.  No host synchronisation: the finalize kernel leaves what the backward needs in a
 // small device buffer (`state`), the upstream gradient is read from device memory.  A term whose weight is 0 is not evaluated
 // (template arguments), so a loss with a dropped term gives the bits of the stand-alone loss.
 //
-// Numerics: softplus(z) = max(z, 0) + log1p(exp(-|z|)); sigmoid(x) and sigmoid(-x) come from one exp(-|x|) (bce_bwd_kernel), and
+// Numerics: softplus(z) = max(z, 0) + log1p(exp(-|z|)); sigmoid(x) and sigmoid(-x) come from one exp(-|x|) (hpri_sigmoids), and
 // (1 - p_t)^gf is formed from 1 - p_t itself, never from 1 - (p_t): a confident correct pixel keeps its relative accuracy.
 //
 // Backward, with G groups and g the upstream gradient:
@@ -33,57 +33,20 @@
 //
 // Edge rules: D == 0 (possible only with s = 0 when every p and y of the group underflows) gives T = 1; T >= 1 gives a term of 0
 // and dL/dT = 0 (for gt < 1 the derivative is unbounded there; targets outside [0, 1] can push T past 1).
-#include "common.h"
+#include "tail_helpers.h"
 #include <math.h>
 
 #define SL_THREADS 256
-#define SL_MAX_BLOCKS 1024          // STEP_MAX_BLOCKS of step.hip
 
 struct SlPoint { float pos_weight, focal_gamma, focal_alpha; };      // the pointwise term's parameters
 
-// units per image: ceil(quads / 256) slices, while n_img * bpi stays within SL_MAX_BLOCKS (one slice per image beyond that)
+// units per image: ceil(quads / 256) slices, while n_img * bpi stays within HPRI_MAX_BLOCKS (one slice per image beyond that)
 static inline int sl_bpi(int n_img, long long hw) {
   long long b = ((hw + 3) / 4 + SL_THREADS - 1) / SL_THREADS;
-  const long long cap = n_img >= SL_MAX_BLOCKS ? 1 : SL_MAX_BLOCKS / n_img;
+  const long long cap = n_img >= HPRI_MAX_BLOCKS ? 1 : HPRI_MAX_BLOCKS / n_img;
   if (b > cap) b = cap;
   if (b < 1) b = 1;
   return (int)b;
-}
-
-static inline int sl_grid(long long units) { return (int)(units < SL_MAX_BLOCKS ? units : SL_MAX_BLOCKS); }
-
-// lanes past cnt read nothing and hold 0
-__device__ __forceinline__ void sl_load4(const float* __restrict__ p, int cnt, int vec, float (&x)[4]) {
-  if (vec) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = v[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) x[j] = j < cnt ? p[j] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void sl_store4(float* __restrict__ p, int cnt, int vec, const float (&x)[4]) {
-  if (vec) {
-    f32x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = x[j];
-    *reinterpret_cast<f32x4*>(p) = v;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j < cnt) p[j] = x[j];
-  }
-}
-
-// sigmoid(x), sigmoid(-x) and log1p(exp(-|x|)) from one exponential
-template <int WITH_LOG>
-__device__ __forceinline__ void sl_sigmoids(float x, float& sp, float& sn, float& lg) {
-  const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
-  sp = x >= 0.f ? r : e * r;
-  sn = x >= 0.f ? e * r : r;
-  lg = WITH_LOG ? log1pf(e) : 0.f;
 }
 
 __device__ __forceinline__ float sl_ce(float x, float y, float lg, float pos_weight) {
@@ -118,13 +81,13 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_fwd_kernel(const float* _
       const long long p0 = q * 4;
       const int cnt = hw - p0 < 4 ? (int)(hw - p0) : 4;
       float xv[4], yv[4];
-      sl_load4(px + p0, cnt, vec, xv);
-      sl_load4(py + p0, cnt, vec, yv);
+      hpri_load4(px + p0, cnt, vec, xv);
+      hpri_load4(py + p0, cnt, vec, yv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < cnt) {
           float sp, sn, lg;
-          sl_sigmoids<POINT>(xv[j], sp, sn, lg);
+          hpri_sigmoids<POINT>(xv[j], sp, sn, lg);
           if (POINT) {
             float v = sl_ce(xv[j], yv[j], lg, pc.pos_weight);
             if (FOCAL) v *= sl_alpha_t(yv[j], pc.focal_alpha) * sl_pow(yv[j] * sn + (1.f - yv[j]) * sp, pc.focal_gamma);
@@ -138,16 +101,7 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_fwd_kernel(const float* _
         }
       }
     }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) red[r][threadIdx.x] = s[r];
-    __syncthreads();
-    for (int w = SL_THREADS / 2; w > 0; w >>= 1) {
-      if (threadIdx.x < w) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[r][threadIdx.x] += red[r][threadIdx.x + w];
-      }
-      __syncthreads();
-    }
+    hpri_block_sum(red, s);
     if (threadIdx.x < 4) partial[(size_t)threadIdx.x * units + unit] = red[threadIdx.x][0];
     __syncthreads();                                    // (red is written again by the block's next unit)
   }
@@ -176,8 +130,7 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_finalize_kernel(const dou
       for (int r = 0; r < 4; ++r) s[r] += partial[(size_t)r * units + u];
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      for (int o = 32; o > 0; o >>= 1) s[r] += __shfl_xor(s[r], o);
+    for (int r = 0; r < 4; ++r) s[r] = hpri_wave_sum(s[r]);
     accp += s[0];
     double c1 = 0.0, c0 = 0.0;
     if (oc.w != 0.0) {
@@ -245,13 +198,13 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_bwd_kernel(const float* _
       const long long p0 = q * 4;
       const int cnt = hw - p0 < 4 ? (int)(hw - p0) : 4;
       float xv[4], yv[4], o[4];
-      sl_load4(px + p0, cnt, vec, xv);
-      sl_load4(py + p0, cnt, vec, yv);
-      // (no j < cnt guard as in the forward: elements past cnt are computed from the zeros sl_load4 left and dropped by sl_store4)
+      hpri_load4(px + p0, cnt, vec, xv);
+      hpri_load4(py + p0, cnt, vec, yv);
+      // (no j < cnt guard as in the forward: elements past cnt are computed from the zeros hpri_load4 left and dropped by hpri_store4)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float sp, sn, lg;
-        sl_sigmoids<(POINT && FOCAL)>(xv[j], sp, sn, lg);
+        hpri_sigmoids<(POINT && FOCAL)>(xv[j], sp, sn, lg);
         const float yy = yv[j];
         float d = 0.f;
         if (POINT) {
@@ -267,7 +220,7 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_bwd_kernel(const float* _
         if (OVERLAP) d += (float)(c1 * (double)yy + c0) * (sp * sn);
         o[j] = d * g;
       }
-      sl_store4(pd + p0, cnt, vec, o);
+      hpri_store4(pd + p0, cnt, vec, o);
     }
   }
 }
@@ -275,8 +228,6 @@ __global__ __launch_bounds__(SL_THREADS) void seg_loss_bwd_kernel(const float* _
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-static inline bool sl_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // the checks shared by the forward and the backward (written so that a NaN fails them)
 static int sl_check(int n_img, long long hw, float w_point, float pos_weight, float focal_gamma, float focal_alpha, float w_overlap) {
   HPRI_REQUIRE(n_img > 0 && hw > 0, "seg_loss: bad sizes");
@@ -306,7 +257,7 @@ extern "C" size_t hpri_seg_loss_state_doubles(int n_img, int per_image) {
     else SL_LAUNCH(KERNEL, 0, 0, 1, __VA_ARGS__);                                                                             \
   } while (0)
 #define SL_LAUNCH(KERNEL, P, F, O, ...) \
-  hipLaunchKernelGGL((KERNEL<P, F, O>), dim3(sl_grid(units)), dim3(SL_THREADS), 0, stream, __VA_ARGS__)
+  hipLaunchKernelGGL((KERNEL<P, F, O>), dim3(hpri_grid_capped(units, 1)), dim3(SL_THREADS), 0, stream, __VA_ARGS__)
 
 extern "C" int hpri_seg_loss_fwd(const float* logits, const float* target, int n_img, long long hw, float w_point, float pos_weight,
                                  float focal_gamma, float focal_alpha, int mean, float w_overlap, float tversky_alpha,
@@ -322,7 +273,7 @@ extern "C" int hpri_seg_loss_fwd(const float* logits, const float* target, int n
   const long long units = (long long)n_img * bpi;
   if (4 * (size_t)units > ws_doubles) return hpri_set_error(HPRI_ERR_WORKSPACE, "seg_loss_fwd: workspace too small");
   if (hpri_seg_loss_state_doubles(n_img, per_image) > state_doubles) return hpri_set_error(HPRI_ERR_WORKSPACE, "seg_loss_fwd: state buffer too small");
-  const int vec = hw % 4 == 0 && sl_aligned16(logits) && sl_aligned16(target);
+  const int vec = hw % 4 == 0 && hpri_aligned16(logits, target);
   const SlPoint pc = {pos_weight, focal_gamma, focal_alpha};
   SL_DISPATCH(seg_loss_fwd_kernel, logits, target, hw, bpi, units, vec, pc, workspace);
   HPRI_CHECK_LAUNCH();
@@ -342,7 +293,7 @@ extern "C" int hpri_seg_loss_bwd(const float* logits, const float* target, int n
   if (hpri_seg_loss_state_doubles(n_img, per_image) > state_doubles) return hpri_set_error(HPRI_ERR_WORKSPACE, "seg_loss_bwd: state buffer too small");
   const int bpi = sl_bpi(n_img, hw);
   const long long units = (long long)n_img * bpi;
-  const int vec = hw % 4 == 0 && sl_aligned16(logits) && sl_aligned16(target) && sl_aligned16(dlogits);
+  const int vec = hw % 4 == 0 && hpri_aligned16(logits, target, dlogits);
   const SlPoint pc = {pos_weight, focal_gamma, focal_alpha};
   SL_DISPATCH(seg_loss_bwd_kernel, logits, target, hw, bpi, units, vec, pc, per_image ? 1 : 0, state, grad_out, dlogits);
   HPRI_CHECK_LAUNCH();

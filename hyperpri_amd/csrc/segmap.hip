@@ -18,8 +18,8 @@
 // CubeStager hand out (band stride 1, pixel stride cs) and a plain contiguous (N, C, h, w) tensor.  Memory-bound and tiny:
 // one lane owns four consecutive pixels of a row -- 16-byte loads of its four predictions and mask values where the quad is
 // 16-byte aligned, its twelve band loads issued before any arithmetic, 12 contiguous bytes out -- and a per-pixel tail
-// covers w % 4.  No LDS, no atomics; the grid is capped at eight workgroups per CU with a grid-stride loop (as cache.hip).
-#include "common.h"
+// covers w % 4.  No LDS, no atomics; the grid is capped at eight workgroups per CU with a grid-stride loop.
+#include "tail_helpers.h"
 
 #define SEGMAP_THREADS 256
 
@@ -161,10 +161,8 @@ extern "C" int hpri_segmap_overlay(const float* image, long long sn, long long s
   a.inv_gamma = inv_gamma; a.alpha = alpha; a.rgb = rgb; a.classes = classes;
   a.vec = (((uintptr_t)pred | (uintptr_t)mask) & 15) == 0 && (((uintptr_t)rgb | (uintptr_t)classes) & 3) == 0;
   const long long items = (long long)N * h * ((w + 3) / 4);
-  long long blocks = (items + SEGMAP_THREADS - 1) / SEGMAP_THREADS;
-  const long long cap = 8LL * hpri_cu_count();                      // eight workgroups per CU, grid-stride over the rest
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(segmap_overlay_kernel, dim3((unsigned)blocks), dim3(SEGMAP_THREADS), 0, stream, a);
+  // (items >= 1 after the size checks above: the floor of hpri_grid_per_cu never acts)
+  hipLaunchKernelGGL(segmap_overlay_kernel, dim3(hpri_grid_per_cu(items, SEGMAP_THREADS, 8)), dim3(SEGMAP_THREADS), 0, stream, a);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;
 }
@@ -276,10 +274,7 @@ extern "C" int hpri_segmap_classes(const float* image, long long sn, long long s
   a.gamma_is_one = gamma == 1.f; a.inv_gamma = inv_gamma; a.alpha = alpha; a.rgb = rgb;
   a.vec = (((uintptr_t)classes | (uintptr_t)rgb) & 3) == 0;
   const long long items = (long long)N * h * ((w + 3) / 4);
-  long long blocks = (items + SEGMAP_THREADS - 1) / SEGMAP_THREADS;
-  const long long cap = 8LL * hpri_cu_count();
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(segmap_classes_kernel, dim3((unsigned)blocks), dim3(SEGMAP_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(segmap_classes_kernel, dim3(hpri_grid_per_cu(items, SEGMAP_THREADS, 8)), dim3(SEGMAP_THREADS), 0, stream, a);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;
 }

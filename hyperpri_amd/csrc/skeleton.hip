@@ -13,7 +13,7 @@
 // 3x3 maximum slides down the column: 3 LDS reads per pixel and level).  Cells outside the image hold NaN in both planes and are
 // never written: fminf / fmaxf return their other operand, which is "the in-image part of the neighbourhood".  For the backward the
 // launch leaves I_1 .. I_{iters+1} and S_0 .. S_{iters-1} of the tile's interior ("saved": 2 iters + 1 planes).  Two image lists go
-// through one launch: the first may be logits (the sigmoid is applied as the tile is loaded, in the exp(-|x|) form of segloss.hip,
+// through one launch: the first may be logits (the sigmoid is applied as the tile is loaded, in the exp(-|x|) form of hpri_sigmoids,
 // and written once), the second is never saved -- the prediction and the target of the loss.
 //
 // Backward: one launch per level, j = iters .. 0 (soft_skel_bwd_kernel), carrying gS (gradient wrt S_j) and gE (wrt I_{j+1}):
@@ -33,7 +33,7 @@
 //   gSp[u] = a y[u] + b,   direct gp[u] = c Sy[u],   dx = g (skeleton-backward(gSp) + gp) sigmoid(x) sigmoid(-x)
 // which the first and the last level launch of the backward read from device memory: no host round trip.  Edge rules: a ratio with
 // a zero denominator (s = 0 and an empty skeleton) is 0 with zero coefficients; tprec + tsens == 0 gives cl = 1, zero coefficients.
-#include "common.h"
+#include "tail_helpers.h"
 #include <math.h>
 
 #define SK_T 64                      // forward tile
@@ -45,12 +45,6 @@
 #define SK_BL (SK_BT + 2 * SK_BH)
 #define SK_BCELLS (SK_BL * SK_BL)
 #define SK_NONE 255
-
-__device__ __forceinline__ void sk_sigmoids(float x, float& sp, float& sn) {        // sl_sigmoids of segloss.hip
-  const float e = expf(-fabsf(x)), r = 1.f / (1.f + e);
-  sp = x >= 0.f ? r : e * r;
-  sn = x >= 0.f ? e * r : r;
-}
 
 // ------------------------------------------------------------------------------------------------
 // Forward
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(SK_THREADS) void soft_skel_fwd_kernel(SkFwd a) {
         v = src[(size_t)gy * a.w + gx];
         if (sig) {
           float sp, sn;
-          sk_sigmoids(v, sp, sn);
+          hpri_sigmoids(v, sp, sn);
           v = sp;
           if (a.p_out && r >= H && r < H + SK_T && c >= H && c < H + SK_T) a.p_out[ioff + (size_t)gy * a.w + gx] = v;
         }
@@ -153,7 +147,7 @@ __global__ __launch_bounds__(SK_THREADS) void soft_skel_fwd_kernel(SkFwd a) {
       if (So) So[g] = S[k];
       if (a.partial) {
         float o = other[g];
-        if (!first) { float sp, sn; sk_sigmoids(o, sp, sn); o = sp; }
+        if (!first) { float sp, sn; hpri_sigmoids(o, sp, sn); o = sp; }
         s0 += (double)S[k] * (double)o;
         s1 += (double)S[k];
       }
@@ -161,14 +155,10 @@ __global__ __launch_bounds__(SK_THREADS) void soft_skel_fwd_kernel(SkFwd a) {
   }
   if (a.partial) {
     __syncthreads();                                       // the planes are done with
-    double* red = sk_lds_d;
-    red[threadIdx.x] = s0; red[SK_THREADS + threadIdx.x] = s1;
-    __syncthreads();
-    for (int wd = SK_THREADS / 2; wd > 0; wd >>= 1) {
-      if ((int)threadIdx.x < wd) { red[threadIdx.x] += red[threadIdx.x + wd]; red[SK_THREADS + threadIdx.x] += red[SK_THREADS + threadIdx.x + wd]; }
-      __syncthreads();
-    }
-    if (threadIdx.x < 2) a.partial[((size_t)img * gridDim.x + tile) * 2 + threadIdx.x] = red[threadIdx.x * SK_THREADS];
+    double (*red)[SK_THREADS] = reinterpret_cast<double (*)[SK_THREADS]>(sk_lds_d);      // two rows; the planes are far larger
+    const double s2[2] = {s0, s1};
+    hpri_block_sum(red, s2);
+    if (threadIdx.x < 2) a.partial[((size_t)img * gridDim.x + tile) * 2 + threadIdx.x] = red[threadIdx.x][0];
   }
 }
 
@@ -194,8 +184,7 @@ __global__ __launch_bounds__(SK_THREADS) void cldice_finalize_kernel(const doubl
       v[0] += pp[0]; v[1] += pp[1]; v[2] += pt[0]; v[3] += pt[1];
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      for (int o = 32; o > 0; o >>= 1) v[r] += __shfl_xor(v[r], o);
+    for (int r = 0; r < 4; ++r) v[r] = hpri_wave_sum(v[r]);
     const double dp = v[1] + s, dt = v[3] + s;
     const double tp = dp == 0.0 ? 0.0 : (v[0] + s) / dp, ts = dt == 0.0 ? 0.0 : (v[2] + s) / dt;
     const double sum = tp + ts;
@@ -325,7 +314,7 @@ __global__ __launch_bounds__(SK_THREADS) void soft_skel_bwd_kernel(SkBwd a) {
       const size_t g = ioff + (size_t)gy * a.w + gx;
       if (a.x) {
         float sp, sn;
-        sk_sigmoids(a.x[g], sp, sn);
+        hpri_sigmoids(a.x[g], sp, sn);
         out = (a.gout ? a.gout[0] : 1.f) * ((out + (float)(ccf * (double)a.Sy[g])) * (sp * sn));
       }
       a.gI_out[g] = out;
@@ -348,7 +337,7 @@ __global__ __launch_bounds__(SK_THREADS) void centerline_count_kernel(const unsi
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    for (int o = 32; o > 0; o >>= 1) v[r] += __shfl_xor(v[r], o);
+    v[r] = hpri_wave_sum(v[r]);
     if ((threadIdx.x & 63) == 0 && v[r]) atomicAdd(counts + 4 * (size_t)blockIdx.y + r, v[r]);
   }
 }

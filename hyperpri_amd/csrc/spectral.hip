@@ -435,7 +435,7 @@ static int band_check(const BandPass& p, const void* workspace, size_t workspace
   CACHE_REQUIRE(p.who, p.select >= 0 && p.select <= 2, "select must be 0 (all), 1 (foreground) or 2 (background)");
   CACHE_REQUIRE(p.who, p.select == 0 || p.masks, "a selection needs the masks");
   CACHE_REQUIRE(p.who, workspace_bytes >= need, "the workspace is smaller than hpri_band_workspace_bytes");
-  CACHE_REQUIRE(p.who, cache_aligned16(p.cache, workspace) && ((uintptr_t)p.table & 3) == 0, "buffers must be 16-byte aligned");
+  CACHE_REQUIRE(p.who, hpri_aligned16(p.cache, workspace) && ((uintptr_t)p.table & 3) == 0, "buffers must be 16-byte aligned");
   return HPRI_OK;
 }
 
@@ -513,7 +513,7 @@ extern "C" int hpri_band_project(const float* x, long long pixels, int cs, const
   const int ks = (K + 7) & ~7;
   const size_t lds = band_project_lds(cs, ks);
   HPRI_REQUIRE(lds <= BAND_LDS_BYTES, "band_project: weights and a tile of this cs and K do not fit the LDS");
-  HPRI_REQUIRE(cache_aligned16(x, weight, bias, y), "band_project: buffers must be 16-byte aligned");
+  HPRI_REQUIRE(hpri_aligned16(x, weight, bias, y), "band_project: buffers must be 16-byte aligned");
   const long long tiles = (pixels + PROJ_TILE - 1) / PROJ_TILE;
   const long long per_cu = BAND_LDS_BYTES / (long long)lds;
   const dim3 grid = cache_grid(tiles, (int)(per_cu < 1 ? 1 : per_cu > 4 ? 4 : per_cu));
@@ -542,7 +542,7 @@ extern "C" int hpri_band_affine(const float* x, long long pixels, int cs, int C,
   HPRI_REQUIRE(x && scale && shift && y, "band_affine: null pointer");
   HPRI_REQUIRE(pixels > 0, "band_affine: bad sizes");
   HPRI_REQUIRE(cs > 0 && cs % 8 == 0 && C > 0 && C <= cs, "band_affine: the channel stride must be a multiple of 8 that holds the bands");
-  HPRI_REQUIRE(cache_aligned16(x, y), "band_affine: buffers must be 16-byte aligned");
+  HPRI_REQUIRE(hpri_aligned16(x, y), "band_affine: buffers must be 16-byte aligned");
   const long long quads = pixels * (cs / 4);
   hipLaunchKernelGGL(band_affine_kernel, cache_grid((quads + 255) / 256, 8), dim3(256), 0, stream, x, quads, cs / 4, C, scale, shift, y);
   HPRI_CHECK_LAUNCH();

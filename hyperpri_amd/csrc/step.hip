@@ -6,10 +6,9 @@
 //   * optim.Adam / optim.SGD over all parameter tensors in one launch (multi-tensor, PLTrainer.py:171-181).
 // All of it is HBM-bound (1 channel of logits; 125 MB of parameters): one pass per tensor, fixed-order reductions
 // (fp64 partials; integer atomics only), no host synchronisation (scalars stay on the device).
-#include "common.h"
+#include "tail_helpers.h"
 
 #define STEP_THREADS 256
-#define STEP_MAX_BLOCKS 1024
 
 // ------------------------------------------------------------------------------------------------
 // BCE-with-logits, mean reduction:  l(x, y) = max(x, 0) - x*y + log1p(exp(-|x|))
@@ -23,31 +22,21 @@ __device__ __forceinline__ float sigmoid_f32(float x) { return 1.f / (1.f + expf
 // partial[b] = fp64 sum of this block's grid-stride slice (fixed slice -> fixed result)
 __global__ __launch_bounds__(STEP_THREADS) void bce_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                long long n, double* __restrict__ partial) {
-  __shared__ double red[STEP_THREADS];
-  double s = 0.0;
+  __shared__ double red[1][STEP_THREADS];
+  double s[1] = {0.0};
   for (long long i = (long long)blockIdx.x * STEP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * STEP_THREADS)
-    s += (double)bce_elem(x[i], y[i]);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = STEP_THREADS / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+    s[0] += (double)bce_elem(x[i], y[i]);
+  hpri_block_sum(red, s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0][0];
 }
 
 __global__ __launch_bounds__(STEP_THREADS) void bce_finalize_kernel(const double* __restrict__ partial, int nblk, long long n,
                                                                     float* __restrict__ loss) {
-  __shared__ double red[STEP_THREADS];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += STEP_THREADS) s += partial[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = STEP_THREADS / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = (float)(red[0] / (double)n);
+  __shared__ double red[1][STEP_THREADS];
+  double s[1] = {0.0};
+  for (int i = threadIdx.x; i < nblk; i += STEP_THREADS) s[0] += partial[i];
+  hpri_block_sum(red, s);
+  if (threadIdx.x == 0) loss[0] = (float)(red[0][0] / (double)n);
 }
 
 // dx = (sigmoid(x) - y) * g / n   (g: upstream scalar gradient on the device, nullptr = 1), evaluated as
@@ -57,19 +46,14 @@ __global__ void bce_bwd_kernel(const float* __restrict__ x, const float* __restr
   const float g = (gout ? gout[0] : 1.f) / (float)n;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
   {
-    const float xi = x[i], yi = y[i];
-    const float e = expf(-fabsf(xi)), r = 1.f / (1.f + e);
-    const float sp = xi >= 0.f ? r : e * r, sn = xi >= 0.f ? e * r : r;     // sigmoid(x), sigmoid(-x)
+    const float yi = y[i];
+    float sp, sn;
+    hpri_sigmoids(x[i], sp, sn);
     dx[i] = ((1.f - yi) * sp - yi * sn) * g;
   }
 }
 
-static inline int step_blocks(long long n) {
-  long long b = (n + STEP_THREADS * 4 - 1) / (STEP_THREADS * 4);
-  if (b > STEP_MAX_BLOCKS) b = STEP_MAX_BLOCKS;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+static inline int step_blocks(long long n) { return hpri_grid_capped(n, STEP_THREADS * 4); }
 
 extern "C" size_t hpri_bce_workspace_doubles(long long n) { return (size_t)step_blocks(n); }
 
@@ -111,22 +95,13 @@ extern "C" int hpri_bce_logits_bwd(const float* logits, const float* target, lon
 __global__ __launch_bounds__(STEP_THREADS) void seg_counts_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                   long long n, float thr, int is_logits,
                                                                   unsigned long long* __restrict__ counts) {
-  __shared__ unsigned int red[4];
-  if (threadIdx.x < 4) red[threadIdx.x] = 0;
-  __syncthreads();
-  unsigned int c[4] = {0, 0, 0, 0};
-  for (long long i = (long long)blockIdx.x * STEP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * STEP_THREADS) {
-    const float p = is_logits ? sigmoid_f32(x[i]) : x[i];
-    const int seg = p > thr, pos = ((int)y[i]) != 0;
-    c[(seg ? 0 : 2) + (pos ? 0 : 1)] += 1;   // seg&pos -> 0 (TP); seg&!pos -> 1 (FP); !seg&pos -> 2 (FN); !seg&!pos -> 3 (TN)
-  }
-  for (int k = 0; k < 4; ++k) {
-    unsigned int v = c[k];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&red[k], v);
-  }
-  __syncthreads();
-  if (threadIdx.x < 4 && red[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)red[threadIdx.x]);
+  hpri_block_count4(counts, [&](unsigned int (&c)[4]) {
+    for (long long i = (long long)blockIdx.x * STEP_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * STEP_THREADS) {
+      const float p = is_logits ? sigmoid_f32(x[i]) : x[i];
+      const int seg = p > thr, pos = ((int)y[i]) != 0;
+      c[(seg ? 0 : 2) + (pos ? 0 : 1)] += 1;   // seg&pos -> 0 (TP); seg&!pos -> 1 (FP); !seg&pos -> 2 (FN); !seg&!pos -> 3 (TN)
+    }
+  });
 }
 
 extern "C" int hpri_seg_counts(const float* pred, const float* target, long long n, float threshold, int is_logits,
