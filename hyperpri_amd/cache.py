@@ -110,7 +110,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _p, _rup
+from ._args import _p, _rup
 
 _log = logging.getLogger("hyperpri_amd")
 _DT = {torch.float32: 0, torch.float16: 1}

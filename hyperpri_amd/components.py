@@ -18,49 +18,17 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _p, _require_cuda, _stream
+from ._args import _as_images, _decision_input, _map3d, _p, _require_cuda, _require_device, _stream
 
 TILE_H, TILE_W = 32, 64         # the tile one workgroup labels in LDS (csrc/components.hip: CC_TILE_H, CC_TILE_W)
 _TRUTH_KIND = {torch.float32: 0, torch.uint8: 1, torch.int32: 2}       # hpri_cc_measure's truth_kind (int32: another label map)
 STAT_NAMES = ("components_removed", "pixels_removed", "holes_filled", "pixels_filled")
 
 
-def _require_device(t: torch.Tensor, what: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"hyperpri_amd: {what} is on {t.device}; connected components exist only as HIP kernels for MI355X "
-                           "(no CPU fallback). Move the tensors to a ROCm device.")
-
-
 def _check_connectivity(connectivity: int) -> int:
     if connectivity not in (4, 8):
         raise ValueError(f"components: connectivity must be 4 or 8, got {connectivity!r}")
     return int(connectivity)
-
-
-def _map3d(t: torch.Tensor, who: str) -> torch.Tensor:
-    """(h, w), (N, h, w) or (N, 1, h, w) -> contiguous (N, h, w)."""
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    elif t.dim() == 4 and t.shape[1] == 1:
-        t = t.reshape(t.shape[0], t.shape[2], t.shape[3])
-    if t.dim() != 3 or t.numel() == 0:
-        raise ValueError(f"{who}: need a non-empty (N, h, w), (N, 1, h, w) or (h, w) map, got {tuple(t.shape)}")
-    if t.numel() >= 2 ** 31:
-        raise ValueError(f"{who}: N*h*w must be below 2^31, got {t.numel()}")
-    return t.contiguous()
-
-
-def _decision_input(pred: torch.Tensor, threshold: Optional[float], who: str) -> Tuple[torch.Tensor, int, float]:
-    """The map as the kernels read it: (contiguous (N, h, w) tensor, kind, threshold)."""
-    if threshold is None:
-        _require_device(pred, f"{who} map")
-        if pred.dtype == torch.bool:
-            pred = pred.view(torch.uint8)
-        if pred.dtype != torch.uint8:
-            raise ValueError(f"{who}: without a threshold the input must be a uint8 or bool map, got {pred.dtype}")
-        return _map3d(pred, who), 1, 0.0
-    _require_cuda(pred, f"{who} prediction")
-    return _map3d(pred.detach(), who), 0, float(threshold)
 
 
 def _workspace(x: torch.Tensor) -> torch.Tensor:
@@ -80,6 +48,11 @@ def label_components(pred: torch.Tensor, threshold: Optional[float] = None, is_l
     ``connectivity``: 4 or 8.  Nothing synchronises with the host; there is no CPU fallback."""
     connectivity = _check_connectivity(connectivity)
     x, kind, thr = _decision_input(pred, threshold, "label_components")
+    return _label_launch(x, kind, thr, is_logits, invert, connectivity)
+
+
+def _label_launch(x: torch.Tensor, kind: int, thr: float, is_logits: bool, invert: bool, connectivity: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One ``hpri_cc_label`` over a contiguous (N, h, w) map."""
     N, h, w = (int(s) for s in x.shape)
     with torch.cuda.device(x.device):
         labels = torch.empty((N, h, w), dtype=torch.int32, device=x.device)
@@ -93,15 +66,7 @@ def label_components(pred: torch.Tensor, threshold: Optional[float] = None, is_l
 def _label_truth(mask: torch.Tensor, connectivity: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """``label_components`` of a fp32 truth map under the rule every kernel of the tail reads a mask by: ``int(mask) != 0``."""
     _require_cuda(mask, "truth map")
-    x = _map3d(mask.detach(), "label_components")
-    N, h, w = (int(s) for s in x.shape)
-    with torch.cuda.device(x.device):
-        labels = torch.empty((N, h, w), dtype=torch.int32, device=x.device)
-        counts = torch.empty((N,), dtype=torch.int32, device=x.device)
-        ws = _workspace(x)
-        _lib.call("hpri_cc_label", _p(x), 2, 0.0, 0, 0, N, h, w, _check_connectivity(connectivity), _p(labels), _p(counts), _p(ws),
-                  ws.numel(), _stream())
-    return labels, counts
+    return _label_launch(_map3d(mask.detach(), "label_components"), 2, 0.0, False, False, _check_connectivity(connectivity))
 
 
 def component_table(labels: torch.Tensor, counts: torch.Tensor, truth: Optional[torch.Tensor] = None) -> Dict[str, np.ndarray]:
@@ -193,15 +158,6 @@ def clean_mask(pred: torch.Tensor, threshold: Optional[float], min_area: int = 0
 # ---------------------------------------------------------------------------------------------------
 # The contract restated in numpy (no scipy): the oracle of the GPU tests
 # ---------------------------------------------------------------------------------------------------
-def _as_images(binary) -> Tuple[np.ndarray, bool]:
-    a = np.asarray(binary) != 0
-    if a.ndim == 2:
-        return a[None], True
-    if a.ndim != 3:
-        raise ValueError(f"components: need a (h, w) or (N, h, w) map, got {a.shape}")
-    return a, False
-
-
 def _label_image(a: np.ndarray, connectivity: int) -> Tuple[np.ndarray, int]:
     """Union-find over one (h, w) boolean image with parent[i] <= i; labels = rank of the root in raster order."""
     h, w = a.shape

@@ -39,8 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .components import _as_images, _decision_input, _map3d, _require_device
-from .engine import _p, _stream
+from ._args import _as_images, _decision_input, _map3d, _p, _require_device, _stream
 
 SITES = {"background": 0, "foreground": 1, "boundary": 2}
 COL_THREADS = 256           # columns one workgroup of the column pass sweeps (csrc/distance.hip: DT_THREADS)

@@ -33,8 +33,8 @@ and diameter of the predicted and the true roots:
 
     surf = surface_metrics(pred, val["best_threshold"], tolerances=(1.0, 2.0)); traits = root_traits(pred, val["best_threshold"])
 
-Lightning-free and torchmetrics-free like ``trainer.py``, whose device pieces this module composes (``hpri_bce_logits_fwd``,
-``SegCounts``, ``PRCurve``, ``best_dice_threshold``, ``average_precision``); the maps are one kernel of their own
+Lightning-free and torchmetrics-free like ``trainer.py``; the device pieces this module composes are those of ``metrics.py``
+(``SegCounts``, ``PRCurve``, ``best_dice_threshold``, ``average_precision``) and ``hpri_bce_logits_fwd``; the maps are one kernel of their own
 (``csrc/segmap.hip``).  There is no CPU fallback: tensors must be fp32 on a ROCm device.
 """
 from __future__ import annotations
@@ -48,10 +48,11 @@ import torch
 from torch import nn
 
 from . import _lib
-from .engine import _p, _require_cuda, _stream
+from ._args import (MAX_CLASSES, _TARGET_KIND, _as_f32, _class_logits, _class_target, _ignore_args, _image4d, _p, _require_cuda,
+                    _require_placed, _stream)
+from .metrics import (PRCurve, SegCounts, _confusion_pass, _split_counts, average_precision, best_dice_threshold,
+                      multiclass_metrics_from_confusion)
 from .tta import TTA, VIEW_CODES, apply_view, view_shape
-from .trainer import (MAX_CLASSES, PRCurve, SegCounts, _TARGET_KIND, _class_logits, _class_target, _confusion_pass, _ignore_args,
-                      _split_counts, average_precision, best_dice_threshold, multiclass_metrics_from_confusion)
 
 # eval_color_segmaps, restated as data: the colour-blind palette (PLTrainer.py:255-258: prediction only, truth only, both), the
 # overlay's alpha (:264), the bands shown as R (700 nm), G (546 nm), B (436 nm) of the band-sliced cube and its gamma (:238-239)
@@ -83,9 +84,7 @@ class SplitPrediction:
 
 def _require_device(t: torch.Tensor, what: str) -> None:
     """``_require_cuda`` for masks, which may be integer tensors: only the placement is checked."""
-    if not t.is_cuda:
-        raise RuntimeError(f"hyperpri_amd: {what} is on {t.device}; evaluation exists only as HIP kernels for MI355X "
-                           "(no CPU fallback). Move the batches to a ROCm device.")
+    _require_placed(t, what, "evaluation exists", "Move the batches to a ROCm device.")
 
 
 def _names(index, n: int) -> List[object]:
@@ -205,25 +204,22 @@ def predict_split(network: nn.Module, batches: Iterable[dict], tta: Optional[TTA
                     logits.append(merged.reshape(-1))
                     if sp is not None:
                         spreads.append(sp.reshape(-1))
-                    for _ in range(n):
-                        offsets.append(offsets[-1] + h * w)
-                        sizes.append((h, w))
-                    continue
-                image, mask = batch["image"], batch["mask"]
-                _require_cuda(image, "evaluation image")
-                _require_device(mask, "evaluation mask")
-                pred = network(image)
-                if isinstance(pred, tuple):                  # analyze=True networks return (pred, features)
-                    pred = pred[0]
-                n = int(pred.shape[0])
-                h, w = int(pred.shape[-2]), int(pred.shape[-1])
-                if pred.numel() != n * h * w or mask.numel() != n * h * w:
-                    raise ValueError(f"evaluate: need one logit and one mask value per pixel, got logits {tuple(pred.shape)} "
-                                     f"and a mask {tuple(mask.shape)}")
-                # copies: a cache hands out views of buffers it rewrites two batches later
-                logits.append(pred.detach().to(torch.float32).reshape(-1).clone())
-                masks.append(mask.to(torch.float32).reshape(-1).clone())
-                names.extend(_names(batch.get("index"), n))
+                else:
+                    image, mask = batch["image"], batch["mask"]
+                    _require_cuda(image, "evaluation image")
+                    _require_device(mask, "evaluation mask")
+                    pred = network(image)
+                    if isinstance(pred, tuple):                  # analyze=True networks return (pred, features)
+                        pred = pred[0]
+                    n = int(pred.shape[0])
+                    h, w = int(pred.shape[-2]), int(pred.shape[-1])
+                    if pred.numel() != n * h * w or mask.numel() != n * h * w:
+                        raise ValueError(f"evaluate: need one logit and one mask value per pixel, got logits {tuple(pred.shape)} "
+                                         f"and a mask {tuple(mask.shape)}")
+                    # copies: a cache hands out views of buffers it rewrites two batches later
+                    logits.append(pred.detach().to(torch.float32).reshape(-1).clone())
+                    masks.append(mask.to(torch.float32).reshape(-1).clone())
+                    names.extend(_names(batch.get("index"), n))
                 for _ in range(n):
                     offsets.append(offsets[-1] + h * w)
                     sizes.append((h, w))
@@ -317,6 +313,13 @@ def test_net(pred: SplitPrediction, best_threshold: float) -> Dict[str, object]:
 test_net.__test__ = False       # (a public name of the reference, not a pytest case)
 
 
+def _shown(C: int, bands: Optional[Sequence[int]], gamma: Optional[float]) -> Tuple[List[int], float]:
+    """The bands shown as R, G, B and their gamma; by default those of the band-sliced HSI cube for C > 3, of an RGB image otherwise."""
+    bands = (HSI_BANDS if C > 3 else RGB_BANDS) if bands is None else bands
+    gamma = (HSI_GAMMA if C > 3 else RGB_GAMMA) if gamma is None else gamma
+    return [int(b) for b in bands], float(gamma)
+
+
 def color_segmaps(image: torch.Tensor, logits: torch.Tensor, mask: torch.Tensor, threshold: float,
                   bands: Optional[Sequence[int]] = None, gamma: Optional[float] = None, alpha: float = ALPHA,
                   palette: Optional[Sequence[Sequence[float]]] = None, return_classes: bool = False):
@@ -332,28 +335,18 @@ def color_segmaps(image: torch.Tensor, logits: torch.Tensor, mask: torch.Tensor,
     _require_cuda(image, "segmentation-map image")
     _require_cuda(logits, "segmentation-map prediction")
     _require_device(mask, "segmentation-map mask")
-    if image.dim() == 5:                # CubeNET cube (N,1,C,h,w) -> (N,C,h,w), as autograd._as4d
-        if image.shape[1] != 1:
-            raise RuntimeError("hyperpri_amd: 5-D input must be (N,1,D,H,W)")
-        image = image.reshape(image.shape[0], image.shape[2], image.shape[3], image.shape[4])
-    if image.dim() != 4:
-        raise ValueError(f"color_segmaps: need a (N,C,h,w) image or a (N,1,C,h,w) cube, got {tuple(image.shape)}")
+    image = _image4d(image, "color_segmaps")
     N, C, h, w = (int(s) for s in image.shape)
     if logits.numel() != N * h * w or mask.numel() != N * h * w:
         raise ValueError(f"color_segmaps: need {N}x{h}x{w} predictions and mask values, got {tuple(logits.shape)} and "
                          f"{tuple(mask.shape)}")
-    if bands is None:
-        bands = HSI_BANDS if C > 3 else RGB_BANDS
-    if gamma is None:
-        gamma = HSI_GAMMA if C > 3 else RGB_GAMMA
-    bands = [int(b) for b in bands]
+    bands, gamma = _shown(C, bands, gamma)
     pal = [float(v) for colour in (PALETTE if palette is None else palette) for v in colour]
     if len(bands) != 3 or len(pal) != 9:
         raise ValueError("color_segmaps: need three band indices and a palette of three R, G, B colours")
-    gamma = float(gamma)
     with torch.cuda.device(image.device):
         x = logits.detach().reshape(N, h, w).contiguous()
-        y = (mask if mask.dtype == torch.float32 else mask.to(torch.float32)).reshape(N, h, w).contiguous()
+        y = _as_f32(mask).reshape(N, h, w).contiguous()
         rgb = torch.empty((N, h, w, 3), dtype=torch.uint8, device=image.device)
         classes = torch.empty((N, h, w), dtype=torch.uint8, device=image.device) if return_classes else None
         sn, sc, sy, sx = image.stride()
@@ -439,16 +432,6 @@ def default_class_palette(num_classes: int) -> Tuple[Tuple[float, float, float],
     return tuple(rows)
 
 
-def _image4d(image: torch.Tensor, who: str) -> torch.Tensor:
-    if image.dim() == 5:                # CubeNET cube (N,1,C,h,w) -> (N,C,h,w), as autograd._as4d
-        if image.shape[1] != 1:
-            raise RuntimeError("hyperpri_amd: 5-D input must be (N,1,D,H,W)")
-        image = image.reshape(image.shape[0], image.shape[2], image.shape[3], image.shape[4])
-    if image.dim() != 4:
-        raise ValueError(f"{who}: need a (N,C,h,w) image or a (N,1,C,h,w) cube, got {tuple(image.shape)}")
-    return image
-
-
 def color_classmaps(image: torch.Tensor, classes: torch.Tensor, palette: Optional[Sequence[Sequence[float]]] = None,
                     alpha: float = ALPHA, bands: Optional[Sequence[int]] = None, gamma: Optional[float] = None) -> torch.Tensor:
     """The multi-class picture (``hpri_segmap_classes``): the device uint8 (N, h, w, 3) picture of ``image``'s three ``bands``,
@@ -464,17 +447,12 @@ def color_classmaps(image: torch.Tensor, classes: torch.Tensor, palette: Optiona
     N, C, h, w = (int(s) for s in image.shape)
     if classes.numel() != N * h * w:
         raise ValueError(f"color_classmaps: need a {N}x{h}x{w} class map, got {tuple(classes.shape)}")
-    if bands is None:
-        bands = HSI_BANDS if C > 3 else RGB_BANDS
-    if gamma is None:
-        gamma = HSI_GAMMA if C > 3 else RGB_GAMMA
-    bands = [int(b) for b in bands]
+    bands, gamma = _shown(C, bands, gamma)
     rows = default_class_palette(MAX_CLASSES) if palette is None else [tuple(float(v) for v in colour) for colour in palette]
     if len(bands) != 3 or any(len(r) != 3 for r in rows) or not 2 <= len(rows) <= MAX_CLASSES:
         raise ValueError(f"color_classmaps: need three band indices and a palette of 2..{MAX_CLASSES} R, G, B colours")
     import ctypes
     pal = (ctypes.c_float * (3 * len(rows)))(*[v for r in rows for v in r])
-    gamma = float(gamma)
     with torch.cuda.device(image.device):
         cls = (classes if classes.dtype == torch.uint8 else classes.to(torch.uint8)).reshape(N, h, w).contiguous()
         rgb = torch.empty((N, h, w, 3), dtype=torch.uint8, device=image.device)
@@ -646,6 +624,17 @@ def clean_prediction(pred: SplitPrediction, threshold: float, min_area: int = 0,
         return cleaned, C.stats_dict(stats)
 
 
+def _to_measure(pred: SplitPrediction, threshold: float, min_area: int, connectivity: int = 8) -> Tuple[SplitPrediction, float, torch.Tensor]:
+    """What the object, surface, trait and centerline metrics read: the split and the threshold to decide it at -- after
+    ``clean_prediction(pred, threshold, min_area)`` when ``min_area > 0``, whose logits any threshold decides alike -- and the
+    masks as fp32."""
+    _require_cuda(pred.logits, "prediction to measure")
+    _require_device(pred.masks, "evaluation mask")
+    if int(min_area) > 0:
+        pred, threshold = clean_prediction(pred, threshold, min_area, 0, connectivity)[0], 0.5
+    return pred, threshold, _as_f32(pred.masks)
+
+
 def object_metrics(pred: SplitPrediction, threshold: float, connectivity: int = 8, min_area: int = 0) -> Dict[str, object]:
     """Count and measure the objects of a stored split: the components of ``sigmoid(logits) > threshold`` (after
     ``clean_prediction(pred, threshold, min_area)`` when ``min_area > 0``) and those of the masks (``int(mask) != 0``), labelled the
@@ -659,12 +648,8 @@ def object_metrics(pred: SplitPrediction, threshold: float, connectivity: int = 
 
     Labelling and measuring run on the device; one small table per group of equal-sized images comes to the host."""
     from . import components as C
-    _require_cuda(pred.logits, "prediction to measure")
-    _require_device(pred.masks, "evaluation mask")
+    pred, threshold, masks = _to_measure(pred, threshold, min_area, connectivity)      # (refuses a bad connectivity when it cleans)
     connectivity = C._check_connectivity(connectivity)
-    if int(min_area) > 0:
-        pred, threshold = clean_prediction(pred, threshold, min_area, 0, connectivity)[0], 0.5
-    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
     tot = {"pred_objects": 0, "pred_objects_hit": 0, "truth_objects": 0, "truth_objects_hit": 0}
     pred_areas: List[List[int]] = []
     truth_areas: List[List[int]] = []
@@ -712,12 +697,8 @@ def surface_metrics(pred: SplitPrediction, threshold: float, tolerances: Sequenc
 
     The distance transforms and histograms run on the device; one histogram per image and direction comes to the host."""
     from . import distance as D
-    _require_cuda(pred.logits, "prediction to measure")
-    _require_device(pred.masks, "evaluation mask")
-    if int(min_area) > 0:
-        pred, threshold = clean_prediction(pred, threshold, min_area, 0)[0], 0.5
+    pred, threshold, masks = _to_measure(pred, threshold, min_area)
     tol = [float(t) for t in tolerances]
-    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
     per = {"hd": [], "hd95": [], "assd": [], "surface_dice": {t: [] for t in tol}}
     undefined = 0
     for i, j in _size_groups(pred):
@@ -742,11 +723,7 @@ def root_traits(pred: SplitPrediction, threshold: float, min_area: int = 0) -> D
     ``length_px``, ``diameter_mean_px``, ``diameter_median_px`` and ``diameter_hist``; the same keys of the masks under ``"truth"``;
     ``names``."""
     from . import distance as D
-    _require_cuda(pred.logits, "prediction to measure")
-    _require_device(pred.masks, "evaluation mask")
-    if int(min_area) > 0:
-        pred, threshold = clean_prediction(pred, threshold, min_area, 0)[0], 0.5
-    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
+    pred, threshold, masks = _to_measure(pred, threshold, min_area)
     out: Dict[str, object] = {name: [] for name in D.TRAIT_NAMES}
     out["truth"] = {name: [] for name in D.TRAIT_NAMES}
     for i, j in _size_groups(pred):
@@ -771,11 +748,7 @@ def centerline_metrics(pred: SplitPrediction, threshold: float, min_area: int = 
 
     Decisions, thinning and counting run on the device; four integers per image come to the host."""
     from . import distance as D
-    _require_cuda(pred.logits, "prediction to measure")
-    _require_device(pred.masks, "evaluation mask")
-    if int(min_area) > 0:
-        pred, threshold = clean_prediction(pred, threshold, min_area, 0)[0], 0.5
-    masks = pred.masks if pred.masks.dtype == torch.float32 else pred.masks.to(torch.float32)
+    pred, threshold, masks = _to_measure(pred, threshold, min_area)
     rows = []
     for i, j in _size_groups(pred):
         a, b, (h, w) = pred.offsets[i], pred.offsets[j], pred.sizes[i]

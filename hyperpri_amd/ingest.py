@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _p, _rup
+from ._args import _p, _rup
 
 
 class CubeStager:

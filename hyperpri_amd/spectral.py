@@ -40,7 +40,7 @@ import torch
 
 from . import _lib
 from .cache import _DT, CubeCache
-from .engine import _p, _rup, _stream
+from ._args import _p, _rup, _stream
 
 FP32_RUN = 2048             # pixels a sum spends in fp32 before it is promoted (csrc/spectral.hip: BAND_FP32_RUN; hpri_band_fp32_run)
 SELECT = {"all": 0, "foreground": 1, "background": 2}
