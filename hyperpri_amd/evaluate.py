@@ -230,6 +230,38 @@ def predict_split(network: nn.Module, batches: Iterable[dict], tta: Optional[TTA
         network.train(was_training)
 
 
+def detect_split(detector: nn.Module, batches: Iterable[dict], score: str = "ace", target: int = 0) -> SplitPrediction:
+    """``predict_split`` for a classical baseline (``hyperpri_amd.SpectralDetector``): the same loop without a network.  Per batch
+    the detector's ``logit=True`` map of ``score`` for target ``target`` (``rx`` has one map) is stored as ``logits`` -- copied, as
+    the cache rewrites its output slots -- with masks, offsets, sizes and names exactly as ``predict_split`` stores them, so
+    ``validate_net``, ``test_net``, ``write_segmaps``, ``clean_prediction``, ``surface_metrics`` and the rest read it unchanged."""
+    logits: List[torch.Tensor] = []
+    masks: List[torch.Tensor] = []
+    offsets, sizes, names = [0], [], []
+    with torch.inference_mode():
+        for batch in batches:
+            image, mask = batch["image"], batch["mask"]
+            _require_cuda(image, "evaluation image")
+            _require_device(mask, "evaluation mask")
+            maps = detector(image, score=score, logit=True)
+            if not 0 <= int(target) < int(maps.shape[1]):
+                raise ValueError(f"detect_split: target {target} of a detector with {int(maps.shape[1])} map(s)")
+            pred = maps[:, int(target)]
+            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
+            if mask.numel() != n * h * w:
+                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
+                                 f"and a mask {tuple(mask.shape)}")
+            logits.append(pred.reshape(-1).clone())
+            masks.append(mask.to(torch.float32).reshape(-1).clone())
+            names.extend(_names(batch.get("index"), n))
+            for _ in range(n):
+                offsets.append(offsets[-1] + h * w)
+                sizes.append((h, w))
+        if not logits:
+            raise ValueError("detect_split: no batches")
+        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+
+
 def _bce(logits: torch.Tensor, masks: torch.Tensor) -> float:
     n = logits.numel()
     nws = _lib.load().hpri_bce_workspace_doubles(n)

@@ -244,6 +244,22 @@ def pca_basis(stats: SpectralStats, k: int, whiten: bool = False, eps: float = 0
 # ---------------------------------------------------------------------------------------------------
 # Projection
 # ---------------------------------------------------------------------------------------------------
+def _band_input(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """(N, C, h, w) -> a tensor whose memory is the (N, h, w, cs) zero-padded channels-last buffer, and cs (shared by
+    ``SpectralProjection`` and ``detect.SpectralDetector``: the zero-copy fast path, else one layout pass plus the pad)."""
+    N, C, h, w = (int(s) for s in t.shape)
+    st = t.stride()
+    cs = int(st[3]) if w > 1 else (int(st[2]) if h > 1 else _rup(C, 8))
+    zero_pad = cs == C or bool(getattr(t, "_hpri_zero_padded", False))
+    if (st[1] == 1 and cs >= C and cs % 8 == 0 and zero_pad and (w == 1 or st[3] == cs) and (h == 1 or st[2] == w * cs)
+            and (N == 1 or st[0] == h * w * cs) and t.data_ptr() % 16 == 0):
+        return t, cs
+    cs = _rup(C, 8)                                              # the slow path: one layout pass, then the pad
+    buf = torch.zeros((N, h, w, cs), dtype=torch.float32, device=t.device)
+    buf[..., :C] = t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+    return buf, cs
+
+
 class SpectralProjection(torch.nn.Module):
     """``y = W x + b`` along the band axis of a device image, as a preprocessing step in front of a network.
 
@@ -314,18 +330,7 @@ class SpectralProjection(torch.nn.Module):
         return self._padded[1], self._padded[2]
 
     def _input(self, t: torch.Tensor) -> Tuple[torch.Tensor, int]:
-        """(N, C, h, w) -> a tensor whose memory is the (N, h, w, cs) zero-padded channels-last buffer, and cs."""
-        N, C, h, w = (int(s) for s in t.shape)
-        st = t.stride()
-        cs = int(st[3]) if w > 1 else (int(st[2]) if h > 1 else _rup(C, 8))
-        zero_pad = cs == C or bool(getattr(t, "_hpri_zero_padded", False))
-        if (st[1] == 1 and cs >= C and cs % 8 == 0 and zero_pad and (w == 1 or st[3] == cs) and (h == 1 or st[2] == w * cs)
-                and (N == 1 or st[0] == h * w * cs) and t.data_ptr() % 16 == 0):
-            return t, cs
-        cs = _rup(C, 8)                                              # the slow path: one layout pass, then the pad
-        buf = torch.zeros((N, h, w, cs), dtype=torch.float32, device=t.device)
-        buf[..., :C] = t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        return buf, cs
+        return _band_input(t)
 
     def forward(self, x):
         if isinstance(x, dict):

@@ -869,6 +869,32 @@ int hpri_band_project(const float* x, long long pixels, int cs, const float* wei
 int hpri_band_affine(const float* x, long long pixels, int cs, int C, const float* scale, const float* shift, float* y,
                      hipStream_t stream);
 
+/* ---- spectral detectors: RX, matched filter, ACE, SAM (detect.hip; hyperpri_amd/detect.py) ------------------------------------
+ * x: the zero-padded channels-last fp32 batch (pixels, cs) hpri_band_project takes (cs % 8 == 0, cs <= hpri_band_max_cs); weight
+ * (ks, cs) and bias (ks) fp32 with zero pad rows and columns: the first Kq <= cs rows are QUADRATIC rows (a whitener), the next
+ * T <= hpri_band_detect_max_targets (8) rows FILTER rows, Kq + T <= ks.  Per pixel
+ *   z[k] = fmaf(W[k][cend-1], x[cend-1], ... fmaf(W[k][0], x[0], b[k]))   every row k < Kq + T (v_mfma_f32_16x16x4_f32: bitwise this chain)
+ *   q    = sum over k < Kq of z[k]^2,      t[j] = z[Kq + j], j < T
+ * cend: a HOST array with one column extent per 16-row block of the Kq + T rows, each a multiple of 8 in [8, cs]; NULL: cs.  The k
+ * loop of a block stops there (a lower-triangular whitener costs about half the MFMAs); for finite inputs the skipped terms are
+ * exact no-ops, so z is the same up to the sign of a zero.  The caller owns the table: W lives on the device and is not inspected,
+ * a table that cuts off a non-zero drops those terms.
+ * The order of q depends on Kq alone (not on the pixel count, the grid or the pixel's place in its tile): with rb the 16-row blocks,
+ * "wave" w in 0 .. 7 owns block 8 r + w in even rounds r and 8 r + 7 - w in odd ones; s(w, kq) = fmaf(z, z, s), from 0, over the
+ * quadratic rows 16 rb + 4 kq + j (j = 0 .. 3) of w's blocks in round order; q = s(0,0) + s(0,1) + s(0,2) + s(0,3) + s(1,0) + ... +
+ * s(7,3), added left to right.  No floating-point atomic: identical arguments give identical bits.
+ * Outputs: q (pixels) fp32, may be NULL; scores (T, pixels) fp32 planes (NULL exactly when T == 0).  score selects what is written,
+ * fused in the epilogue:  0: t[j];  1: the cosine t[j] * rsqrt(q), 0 where q == 0;  2, 3: the logit log(p) - log1p(-p) of 0, 1 with
+ * p = clamp(value, 2^-24, 1 - 2^-24), and then q is written as the logit of p = q / (q + Kq) as well.
+ * Identity metric: weight == NULL (then Kq == 0, cend == NULL): q = fmaf(x[c], x[c], q) from 0 and t[j] = fmaf(F[j][c], x[c], t[j])
+ * from bias[j] (0 with bias == NULL), both ascending c; F = filters, (T, cs) fp32, 16-byte aligned (NULL otherwise and when T == 0).
+ * No matrix unit: one memory-bound sweep with 16-byte loads; q is always written raw.
+ * A bad size, a misaligned pointer, Kq + T not fitting ks, T beyond the maximum, a cs out of range, a bad extent or an unknown score
+ * return -1 before any launch.  hpri_band_detect_max_targets is a pure host query. */
+int hpri_band_detect_max_targets(void);
+int hpri_band_detect(const float* x, long long pixels, int cs, const float* weight, const float* bias, int ks, int Kq, int T,
+                     const float* filters, const int* cend, int score, float* q, float* scores, hipStream_t stream);
+
 /* ---- soft skeletons and the centerline loss clDice (skeleton.hip; hyperpri_amd/trainer.py, distance.py) ------------------------
  * fp32 planes (N, h, w), contiguous, values meant to lie in [0, 1]; 0 <= iters <= hpri_soft_skeleton_max_iters (32).
  *   E(I)[u] = min over the in-image part of the plus neighbourhood {N, W, C, E, S} of u,  D(I)[u] = max over the in-image 3x3
