@@ -5,13 +5,15 @@ Drop-in ``torch.nn.Module`` replacements for the reference's ``src/Experiments/m
 """
 from .cache import (CubeAugment, CubeCache, CubeDeform, deform_entries, elastic_lattice, plan_epoch, plan_epoch_augmented,  # noqa: F401
                     plan_epoch_deformed)
+from .cluster import (ClusterSums, SpectralKMeans, assign_reference, cluster_step, cluster_step_reference, kmeans_reference,  # noqa: F401
+                      merge_cluster_sums)
 from .components import (TILE_H, TILE_W, clean_mask, clean_reference, component_table, components_reference,  # noqa: F401
                          label_components)
 from .detect import SpectralDetector, detect_reference, whitener_reference  # noqa: F401
 from .distance import (boundary_reference, centerline_counts, centerline_from_counts, distance_transform, edt_reference,  # noqa: F401
                        links_reference, root_traits, skeleton_links, skeletonize, soft_skeleton_reference, surface_distances,
                        surface_hist_reference, surface_metrics_from_hist, thin_reference)
-from .evaluate import (CLEAN_LOGIT, SplitPrediction, centerline_metrics, clean_prediction, color_classmaps, color_segmaps,  # noqa: F401
+from .evaluate import (CLEAN_LOGIT, SplitPrediction, centerline_metrics, clean_prediction, cluster_split, color_classmaps, color_segmaps,  # noqa: F401
                        default_class_palette, detect_split, evaluate_multiclass, object_metrics, predict_split, surface_metrics, test_net, tta_merge,
                        validate_net, write_segmaps, write_spreadmaps)
 from .evaluate import root_traits as split_root_traits  # noqa: F401  (``root_traits`` is the per-tensor call of distance.py)

@@ -15,55 +15,16 @@
 // BAND_GRAM_PARTS: constants, not the CU count), one workgroup per partial.  A finishing kernel adds the partials 0, 1, 2, ... in
 // fp64.  No floating-point atomic anywhere: the bits depend on the arguments and on these constants only.  The partials live in the
 // caller's workspace, whose size (hpri_band_workspace_bytes) depends on cs alone.
-#include "cache_launch.h"
+#include "band_common.h"                // BAND_FP32_RUN, BAND_MAX_CS, the loads, the selection, the runs and band_check
 
-#define BAND_FP32_RUN 2048              // pixels a sum spends in fp32 before it is promoted (documented: <= 4096)
 #define BAND_MOMENT_PARTS 2048          // partial accumulators of the moments pass (memory-bound: eight workgroups per CU)
 #define BAND_GRAM_PARTS 256             // partial accumulators of the Gram pass (MFMA-bound: one wave per SIMD)
-#define BAND_MAX_CS 320                 // ten 32-band blocks: 55 block pairs, at most 14 per wave
-#define BAND_THREADS 256
 #define GRAM_CHUNK 16                   // pixels staged in LDS at a time
 #define GRAM_MAXP 14                    // block pairs per wave
 #define GRAM_LOADS ((GRAM_CHUNK * (BAND_MAX_CS / 4) + BAND_THREADS - 1) / BAND_THREADS)
 #define PROJ_TILE 64                    // pixels per workgroup tile: 16 per wave
 #define PROJ_MAX_K 64
 #define PROJ_LOADS ((PROJ_TILE * (BAND_MAX_CS / 4) + BAND_THREADS - 1) / BAND_THREADS)
-#define BAND_LDS_BYTES (160 * 1024)
-
-__device__ __forceinline__ f32x4 band_load(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 band_load(const _Float16* p) {
-  const f16x4 v = *reinterpret_cast<const f16x4*>(p);
-  f32x4 r;
-  r[0] = (float)v[0]; r[1] = (float)v[1]; r[2] = (float)v[2]; r[3] = (float)v[3];
-  return r;
-}
-
-// the same 16 (8) bytes as they come, widened later: a load whose value is not touched does not stall the wave that issued it
-__device__ __forceinline__ f32x4 band_raw(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f16x4 band_raw(const _Float16* p) { return *reinterpret_cast<const f16x4*>(p); }
-__device__ __forceinline__ f32x4 band_widen(f32x4 v) { return v; }
-__device__ __forceinline__ f32x4 band_widen(f16x4 v) {
-  f32x4 r;
-  r[0] = (float)v[0]; r[1] = (float)v[1]; r[2] = (float)v[2]; r[3] = (float)v[3];
-  return r;
-}
-
-__device__ __forceinline__ bool band_selected(const unsigned char* __restrict__ masks, long long pixel, int select) {
-  if (select == 0) return true;
-  return (masks[pixel] != 0) == (select == 1);
-}
-
-struct BandRun { long long base; int len; };     // first pixel (slot * P + offset inside the slot) and length of a run
-
-__device__ __forceinline__ BandRun band_run(const int* __restrict__ table, int slots, long long P, int runs_per_slot, long long r) {
-  const int e = (int)(r / runs_per_slot), k = (int)(r - (long long)e * runs_per_slot);
-  const int slot = min(max(table[e], 0), slots - 1);
-  const long long p0 = (long long)k * BAND_FP32_RUN;
-  BandRun b;
-  b.base = (long long)slot * P + p0;
-  b.len = (int)min((long long)BAND_FP32_RUN, P - p0);
-  return b;
-}
 
 // ---- moments ---------------------------------------------------------------------------------------------------------
 // One workgroup per partial.  Thread t holds channel quad t % q of the pixels t / q, t / q + npl, ... of a run (q = cs / 4,
@@ -423,20 +384,6 @@ extern "C" size_t hpri_band_workspace_bytes(int cs) {
   if (cs <= 0 || cs % 8 != 0 || cs > BAND_MAX_CS) return 0;
   const size_t a = band_moment_bytes(cs), b = band_gram_bytes(cs);
   return a > b ? a : b;
-}
-
-struct BandPass { const char* who; const void* cache; int dtype, slots, Hs, Ws, cs; const unsigned char* masks; const int* table; int n, select; };
-
-static int band_check(const BandPass& p, const void* workspace, size_t workspace_bytes, size_t need) {
-  CACHE_REQUIRE(p.who, p.cache && p.table && workspace, "null pointer");
-  CACHE_REQUIRE(p.who, p.dtype == 0 || p.dtype == 1, "cache_dtype must be 0 (f32) or 1 (f16)");
-  CACHE_REQUIRE(p.who, p.slots > 0 && p.Hs > 0 && p.Ws > 0 && p.n > 0, "bad sizes");
-  CACHE_REQUIRE(p.who, p.cs > 0 && p.cs % 8 == 0 && p.cs <= BAND_MAX_CS, "the channel stride must be a multiple of 8 up to hpri_band_max_cs");
-  CACHE_REQUIRE(p.who, p.select >= 0 && p.select <= 2, "select must be 0 (all), 1 (foreground) or 2 (background)");
-  CACHE_REQUIRE(p.who, p.select == 0 || p.masks, "a selection needs the masks");
-  CACHE_REQUIRE(p.who, workspace_bytes >= need, "the workspace is smaller than hpri_band_workspace_bytes");
-  CACHE_REQUIRE(p.who, hpri_aligned16(p.cache, workspace) && ((uintptr_t)p.table & 3) == 0, "buffers must be 16-byte aligned");
-  return HPRI_OK;
 }
 
 extern "C" int hpri_band_moments(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const unsigned char* masks,

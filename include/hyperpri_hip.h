@@ -895,6 +895,51 @@ int hpri_band_detect_max_targets(void);
 int hpri_band_detect(const float* x, long long pixels, int cs, const float* weight, const float* bias, int ks, int Kq, int T,
                      const float* filters, const int* cend, int score, float* q, float* scores, hipStream_t stream);
 
+/* ---- spectral k-means: assignment and the fitting pass (cluster.hip; hyperpri_amd/cluster.py) ------------------------------------
+ * A generic argmin of K affine scores of a centred pixel; K <= hpri_band_cluster_max_k (64), cs % 8 == 0 and cs <= hpri_band_max_cs.
+ *   d[c]  = fp32(x[c] - pivot[c]), rounded once exactly as hpri_band_gram rounds it; pivot: fp32 (cs), zero pad entries; NULL: d = x
+ *   z[k]  = fmaf(centers[k][cs-1], d[cs-1], ... fmaf(centers[k][0], d[0], bias[k]))   ascending c from the bias: bitwise the chain of
+ *           hpri_band_project (v_mfma_f32_16x16x4_f32 with k = band); centers (ks, cs) fp32, ks = roundup(K, 8), zero pad rows and
+ *           columns; bias (ks) fp32
+ *   label = the lowest k < K with z[k] == min over k < K,  zmin = z[label].  Rows >= K never take part (no infinite bias is needed),
+ *           and label < K holds for every input, non-finite ones included; what a NaN pixel is labelled is otherwise unspecified.
+ * For a centroid g_k the caller passes centers[k] = -g_k and bias[k] = |g_k|^2 / 2; the kernels know nothing of that.
+ *   hpri_band_assign        x: the zero-padded channels-last fp32 batch (pixels, cs) hpri_band_project takes.  Outputs, each may be NULL
+ *                           but not all: labels (pixels) uint8; zmin (pixels) fp32; dist2 (pixels) fp32 = max(0, fmaf(2, zmin, s)) with
+ *                           s = fmaf(d[c], d[c], s) from 0, ascending c (the squared distance to the nearest centroid); value (pixels)
+ *                           fp32 = lut[label], lut: K fp32, given exactly when value is.  One pass; the centres stay in LDS for a
+ *                           workgroup's lifetime (a tile of 64 pixels beside them, 32 where both do not fit: cs > 304 at ks = 64);
+ *                           nothing of size pixels x K is written; the result of a pixel depends neither on the pixel count, nor on
+ *                           the grid, nor on the pixel's place in its tile.
+ *   hpri_band_cluster_sums  over the selected pixels of the listed slots (the leading arguments of hpri_band_gram, fp32 and fp16
+ *                           caches): counts[k] (int64, K) = the pixels with label k, exact; sums[k*cs + c] (fp64, K x cs) = the sum of
+ *                           d[c] over them; totals[0] = the sum of zmin, totals[1] = the sum over pixels and c of d[c]^2 (fp64).  A
+ *                           pixel that is not selected contributes exact zeros and counts nowhere.  The labels are those
+ *                           hpri_band_assign gives the same pixel, bit for bit: same d, same chain, same code.
+ *     Summation: the runs are those of hpri_band_gram (hpri_band_fp32_run pixels).  Inside a run sums[k][c] is the fp32 chain
+ *     acc = fmaf(onehot, d[p][c], acc) from 0 over ALL the run's pixels p in ascending order (v_mfma_f32_32x32x2_f32 with k = pixel,
+ *     onehot = 1 for the pixel's cluster, else 0: a pixel of another cluster, one that is not selected and the zero pad add exact
+ *     zeros).  After the run the chain is added into an fp64 partial; partial a owns the runs a, a + PARTS, ... of the launch in that
+ *     order, PARTS = hpri_band_cluster_parts() = 256, a constant; a finishing kernel adds the partials in ascending order.  zmin and
+ *     the per-pixel s (the fp32 chain above) are added in fp64 pixel by pixel: pixel i of a chunk of 64 (32 with the small tile) of a
+ *     run goes to accumulator i of the run's partial, and the 64 accumulators are added in ascending order before the partials are.
+ *     Counts: integer atomics inside a workgroup, then the partial scheme.  No floating-point atomic: the bits depend on the arguments
+ *     and these constants only, not on the grid or the CU count.
+ *     workspace: hpri_band_cluster_workspace_bytes(cs, K) bytes, 16-byte aligned; a pure host query, a function of its arguments
+ *     alone (0 for a cs or K the pass does not take).
+ * Argument errors (a null pointer, a size <= 0, cs % 8 != 0 or beyond hpri_band_max_cs, K outside [1, hpri_band_cluster_max_k], a select
+ * or dtype out of range, a selection without masks, a workspace that is too small or misaligned, value without lut or lut without
+ * value, no output at all, a misaligned pointer) return -1 before any launch. */
+int hpri_band_cluster_max_k(void);
+int hpri_band_cluster_parts(void);
+size_t hpri_band_cluster_workspace_bytes(int cs, int K);
+int hpri_band_assign(const float* x, long long pixels, int cs, const float* pivot, const float* centers, const float* bias, int K,
+                     const float* lut, unsigned char* labels, float* zmin, float* dist2, float* value, hipStream_t stream);
+int hpri_band_cluster_sums(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const unsigned char* masks,
+                           const int* slot_table, int n, int select, const float* pivot, const float* centers, const float* bias, int K,
+                           void* workspace, size_t workspace_bytes, long long* counts, double* sums, double* totals,
+                           hipStream_t stream);
+
 /* ---- soft skeletons and the centerline loss clDice (skeleton.hip; hyperpri_amd/trainer.py, distance.py) ------------------------
  * fp32 planes (N, h, w), contiguous, values meant to lie in [0, 1]; 0 <= iters <= hpri_soft_skeleton_max_iters (32).
  *   E(I)[u] = min over the in-image part of the plus neighbourhood {N, W, C, E, S} of u,  D(I)[u] = max over the in-image 3x3
