@@ -24,8 +24,9 @@ from .spectral import (SpectralProjection, SpectralStats, band_statistics, class
                        moments_reference, pca_basis, project_reference)
 from .tta import TTA, VIEW_NAMES, apply_view, invert_view, tta_merge_reference  # noqa: F401
 from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss, FocalLoss, forward_loss, FusedAdam, FusedSGD,  # noqa: F401
-                      PRCurve, SegConfusion, SegCounts, SegLoss, SegmentationModel, TverskyLoss, argmax_classes, average_precision,
-                      clDiceLoss, load_checkpoint, multiclass_metrics_from_confusion, network_state_dict, soft_skeleton)
+                      LovaszHingeLoss, PRCurve, SegConfusion, SegCounts, SegLoss, SegmentationModel, TverskyLoss, argmax_classes,
+                      average_precision, clDiceLoss, load_checkpoint, lovasz_hinge_reference, multiclass_metrics_from_confusion,
+                      network_state_dict, ranking_metrics, ranking_reference, soft_skeleton, sort_scores)
 
 __version__ = "0.1.0"
 

@@ -1,5 +1,5 @@
 // The rules the kernels of a step's tail share (step.hip, segmap.hip, multiclass.hip, segloss.hip, components.hip, distance.hip,
-// skeleton.hip, spectral.hip and the cube cache's launchers): every rule once.  They carry the reproducibility promise -- fp64 sums
+// skeleton.hip, spectral.hip, sort.hip and the cube cache's launchers): every rule once.  They carry the reproducibility promise -- fp64 sums
 // in a fixed order, fixed butterflies, integer atomics only -- so a new tail kernel takes them from here and restates none of them.
 #pragma once
 #include "common.h"

@@ -3,6 +3,7 @@
     crit = BCEWithLogitsLoss()                       # drop-in for nn.BCEWithLogitsLoss() (params_HyperPRI.py:60)
     crit = DiceBCELoss(pos_weight=3.0)               # or an imbalance-aware one (csrc/segloss.hip): SegLoss, DiceLoss, TverskyLoss, FocalLoss
     crit = clDiceLoss(iters=3, base=DiceLoss())      # or with the centerline term for thin roots (csrc/skeleton.hip)
+    crit = LovaszHingeLoss()                         # or the convex surrogate of +IoU itself (csrc/sort.hip)
     crit = CrossEntropyLoss(ignore_index=255)        # multi-class (csrc/multiclass.hip)
 
 Each is an autograd function around the HIP library's forward and backward entry points; nothing synchronises with the host.
@@ -10,8 +11,9 @@ There is no CPU fallback: tensors must be fp32 on a ROCm device.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -381,6 +383,119 @@ class clDiceLoss(nn.Module):
 
     def extra_repr(self) -> str:
         return ", ".join(f"{k}={getattr(self, k)}" for k in ("iters", "alpha", "smooth", "per_image"))
+
+
+# ---------------------------------------------------------------------------------------------------
+# The Lovasz hinge on the device sort (csrc/sort.hip)
+# ---------------------------------------------------------------------------------------------------
+def _check_ignore_index(ignore_index, who: str) -> Optional[int]:
+    if ignore_index is None:
+        return None
+    if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or abs(int(ignore_index)) >= 2 ** 24:
+        raise ValueError(f"{who}: ignore_index must be None or an integer an fp32 target can hold exactly, got {ignore_index!r}")
+    return int(ignore_index)
+
+
+class _LovaszHingeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred: torch.Tensor, target: torch.Tensor, per_image: bool, ignore_index: Optional[int]):
+        _require_cuda(pred, "LovaszHingeLoss input")
+        with torch.cuda.device(pred.device):
+            x, y = _flat(pred, "LovaszHingeLoss input"), _flat(_as_f32(target), "LovaszHingeLoss target")
+            if x.shape != y.shape:
+                raise ValueError(f"Target size ({tuple(y.shape)}) must be the same as input size ({tuple(x.shape)})")
+            if x.dim() < 1 or x.numel() == 0:
+                raise ValueError(f"LovaszHingeLoss: need (N, ...) logits with at least one element, got {tuple(x.shape)}")
+            n_img = int(x.shape[0])
+            hw = x.numel() // n_img
+            use_ignore, ignore = _ignore_args(ignore_index)
+            nws = _lib.load().hpri_lovasz_hinge_workspace_bytes(n_img, hw, int(per_image))
+            if nws == 0:
+                raise ValueError(f"LovaszHingeLoss: at most 65535 images and fewer than 2^31 elements, got {tuple(x.shape)}")
+            ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+            loss = torch.empty((), dtype=torch.float32, device=x.device)
+            coef = torch.empty_like(x)
+            _lib.call("hpri_lovasz_hinge_fwd", _p(x), _p(y), n_img, hw, int(per_image), use_ignore, ignore, _p(loss), _p(coef), _p(ws),
+                      nws, _stream())
+            ctx.save_for_backward(coef)
+            ctx.shape = pred.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout: torch.Tensor):
+        coef, = ctx.saved_tensors
+        with torch.cuda.device(coef.device):
+            g = _grad_f32(gout)
+            dx = torch.empty_like(coef)
+            _lib.call("hpri_lovasz_hinge_bwd", _p(coef), coef.numel(), _p(g), _p(dx), _stream())
+        return dx.view(ctx.shape), None, None, None
+
+
+class LovaszHingeLoss(nn.Module):
+    """The Lovasz hinge (Berman et al., CVPR 2018), the convex surrogate of the Jaccard index (+IoU) the reference scores by, over
+    fp32 logits ``x`` of any shape (N, ...) and a target ``y`` of the same shape (``csrc/sort.hip``)::
+
+        s_i = +1 if y_i >= 0.5 else -1,   e_i = 1 - x_i * s_i                                         (fp32)
+        per group: the pixels by e descending, ties in index order;  G1 = the group's positives
+        at rank r:  P_r = positives among ranks 0..r,  I_r = G1 - P_r,  U_r = G1 + (r + 1 - P_r),  J_r = 1 - I_r / U_r
+        loss_g = sum_r relu(e_(r)) * (J_r - J_{r-1}),   loss = mean over the groups
+
+    A group is one image (``per_image=True``, the default of the published code) or the whole batch.  ``ignore_index``: pixels
+    whose target equals it are left out of the order, the counts and the gradient; a group with nothing left contributes 0.  The
+    weights ``J_r - J_{r-1}`` are evaluated without cancellation in fp64 from integer counts (``1 / U_r`` for a positive pixel,
+    ``I_r / ((U_r - 1) U_r)`` for a negative one; ``G1 == 0``: all weight on rank 0) and are constants of the gradient, as in the
+    published code: ``d loss / d x_i = -s_i * w_rank(i) / groups`` where ``e_i > 0`` and exactly 0 elsewhere.  The forward sorts on
+    the device (17 launches, fp64 sums in a fixed order -> bit-reproducible, no host synchronisation) and leaves one coefficient per
+    pixel; the backward is one elementwise launch.  The module sits outside the network's tape, like ``SegLoss``, so it works in
+    every precision mode and as ``SegmentationModel(net, criterion=LovaszHingeLoss())``.  No double backward."""
+
+    def __init__(self, per_image: bool = True, ignore_index: Optional[int] = None):
+        super().__init__()
+        self.per_image = bool(per_image)
+        self.ignore_index = _check_ignore_index(ignore_index, "LovaszHingeLoss")
+
+    def forward(self, input: torch.Tensor, target: torch.Tensor) -> torch.Tensor:   # noqa: A002 (torch's names)
+        return _LovaszHingeFn.apply(input, target, self.per_image, self.ignore_index)
+
+    def extra_repr(self) -> str:
+        return f"per_image={self.per_image}, ignore_index={self.ignore_index}"
+
+
+def lovasz_hinge_reference(x, y, per_image: bool = True, ignore_index: Optional[int] = None) -> Tuple[float, np.ndarray]:
+    """``LovaszHingeLoss`` restated in numpy: (loss, d loss / d x) in fp64 for arrays ``x``, ``y`` of one shape (N, ...).  The errors
+    ``e`` are formed in fp32, as the kernels form them; the order is a stable descending sort; the weights are the closed form."""
+    x32, y32 = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(y, dtype=np.float32)
+    if x32.shape != y32.shape or x32.ndim < 1 or x32.size == 0:
+        raise ValueError(f"lovasz_hinge_reference: need x and y of one shape (N, ...), got {x32.shape} and {y32.shape}")
+    rows = x32.shape[0] if per_image else 1
+    xs, ys = x32.reshape(rows, -1), y32.reshape(rows, -1)
+    grad = np.zeros(xs.shape, dtype=np.float64)
+    total = 0.0
+    for g in range(rows):
+        keep = np.ones(xs.shape[1], dtype=bool) if ignore_index is None else ys[g] != np.float32(ignore_index)
+        at = np.nonzero(keep)[0]
+        if at.size == 0:
+            continue
+        pos = ys[g][at] >= np.float32(0.5)
+        s = np.where(pos, np.float32(1), np.float32(-1)).astype(np.float32)
+        e = (np.float32(1) - xs[g][at] * s).astype(np.float32)
+        order = np.argsort(-e.astype(np.float64), kind="stable")
+        es, ps = e[order].astype(np.float64), pos[order]
+        G1 = int(ps.sum())
+        P = np.cumsum(ps.astype(np.int64))
+        r = np.arange(at.size, dtype=np.int64)
+        U = (G1 + (r + 1 - P)).astype(np.float64)
+        I = (G1 - P).astype(np.float64)                                   # noqa: E741
+        if G1 == 0:
+            w = np.zeros(at.size, dtype=np.float64)
+            w[0] = 1.0
+        else:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                w = np.where(ps, 1.0 / U, I / ((U - 1.0) * U))
+        on = es > 0
+        total += float(np.sum(np.where(on, es, 0.0) * w))
+        grad[g, at[order]] = np.where(on, -s[order].astype(np.float64) * w / rows, 0.0)
+    return total / rows, grad.reshape(x32.shape)
 
 
 def _takes_fused_head(criterion: nn.Module) -> bool:

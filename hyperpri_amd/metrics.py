@@ -8,11 +8,12 @@ from __future__ import annotations
 
 from typing import Callable, Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._args import (MAX_CLASSES, _TARGET_KIND, _as_f32, _class_logits, _class_target, _flat, _ignore_args, _p, _require_cuda,
-                    _stream)
+                    _require_placed, _stream)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -308,3 +309,90 @@ def average_precision(pred: torch.Tensor, target: torch.Tensor) -> float:
     recall = tp / npos
     prev = torch.cat([torch.zeros(1, dtype=torch.float64, device=recall.device), recall[:-1]])
     return float(((recall - prev) * precision).sum())
+
+
+# ---------------------------------------------------------------------------------------------------
+# The device sort and the exact ranking metrics on it (csrc/sort.hip)
+# ---------------------------------------------------------------------------------------------------
+def sort_scores(keys: torch.Tensor, descending: bool = True, groups: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A stable sort of fp32 device keys, read as ``groups`` contiguous groups of equal length: ``(perm, sorted_keys)``, both of
+    shape (groups, L).  ``perm[g]`` holds int32 indices inside group ``g`` and equals, bit for bit, the indices of
+    ``torch.sort(keys[g], descending=descending, stable=True)``: NaN ranks above +inf, -0.0 equals +0.0, ties keep their index
+    order; ``sorted_keys`` are the keys in that order with their original bits.  A radix sort in HIP (15 launches for every size),
+    no host synchronisation."""
+    _require_cuda(keys, "sort_scores keys")
+    groups = int(groups)
+    if groups < 1 or keys.numel() == 0 or keys.numel() % groups:
+        raise ValueError(f"sort_scores: {keys.numel()} keys do not make {groups} non-empty groups of equal length")
+    with torch.cuda.device(keys.device):
+        k = _flat(keys.detach(), "sort_scores keys").reshape(groups, -1)
+        L = int(k.shape[1])
+        nws = _lib.load().hpri_sort_workspace_bytes(groups, L) if k.numel() < 2 ** 31 else 0
+        if nws == 0:
+            raise ValueError(f"sort_scores: at most 65535 groups and fewer than 2^31 keys, got {groups} groups of {L}")
+        ws = torch.empty(nws, dtype=torch.uint8, device=k.device)
+        perm = torch.empty((groups, L), dtype=torch.int32, device=k.device)
+        out = torch.empty_like(k)
+        _lib.call("hpri_sort_keys_f32", _p(k), groups, L, int(bool(descending)), _p(perm), _p(out), _p(ws), nws, _stream())
+    return perm, out
+
+
+def ranking_metrics(scores: torch.Tensor, target: torch.Tensor) -> Dict[str, float]:
+    """The exact ranking metrics of a whole split from ONE device sort of its scores (``csrc/sort.hip``; 17 launches, no ATen kernel
+    beyond the allocations, one 24-byte read at the end)::
+
+        avg_prec  sum over the runs of equal scores, in descending order, of (R_n - R_{n-1}) P_n: the definition ``average_precision``
+                  documents, accumulated in fp64 as sum_runs p_run * tp / (tp + fp), divided by the positives on the host
+        roc_auc   the Mann-Whitney statistic with ties counted half: sum_runs p_run * (2 * negatives ranked below + negatives of the
+                  run) / (2 P N); the numerator is an exact integer (uint64), divided on the host
+
+    ``scores``: fp32 of any shape (the flat tensors of a ``SplitPrediction``; pass ``torch.sigmoid(logits)`` where parity with the
+    reference's AP is wanted: the fp32 sigmoid merges scores into ties, and ties change AP).  ``target``: the same number of
+    elements, non-zero = positive; fp32, uint8 and bool are read as they are, other types are converted once.  ``avg_prec`` is NaN
+    without a positive, ``roc_auc`` when a class is empty.  -0.0 and +0.0 are one score, and so are all NaNs."""
+    _require_cuda(scores, "ranking_metrics scores")
+    with torch.cuda.device(scores.device):
+        s = _flat(scores.detach(), "ranking_metrics scores").reshape(-1)
+        _require_placed(target, "ranking_metrics target")
+        t = target.detach().reshape(-1)
+        if t.dtype == torch.bool:
+            t = t.contiguous().view(torch.uint8)
+        elif t.dtype not in (torch.float32, torch.uint8):
+            t = t.to(torch.float32)
+        t = t.contiguous()
+        n = s.numel()
+        if n == 0 or t.numel() != n:
+            raise ValueError(f"ranking_metrics: need as many targets as scores and at least one, got {n} and {t.numel()}")
+        nws = _lib.load().hpri_ranking_workspace_bytes(n)
+        if nws == 0:
+            raise ValueError(f"ranking_metrics: fewer than 2^31 scores, got {n}")
+        ws = torch.empty(nws, dtype=torch.uint8, device=s.device)
+        out = torch.empty(3, dtype=torch.int64, device=s.device)
+        _lib.call("hpri_ranking_sums", _p(s), _p(t), 0 if t.dtype == torch.float32 else 1, n, _p(out), _p(ws), nws, _stream())
+        host = out.cpu()
+    ap_num = float(host[:1].view(torch.float64)[0])
+    u, p = int(host[1]), int(host[2])
+    return _ranking_from_sums(ap_num, u, p, n)
+
+
+def _ranking_from_sums(ap_num: float, u: int, p: int, n: int) -> Dict[str, float]:
+    neg = n - p
+    return {"avg_prec": ap_num / p if p else float("nan"), "roc_auc": u / (2 * p * neg) if p and neg else float("nan")}
+
+
+def ranking_reference(scores, target) -> Dict[str, float]:
+    """``ranking_metrics`` restated in numpy on the host: integer counts over the runs of equal fp32 scores (the AUC numerator in
+    Python integers, the AP sum in fp64 in run order)."""
+    s = np.asarray(scores, dtype=np.float32).reshape(-1)
+    t = np.asarray(target).reshape(-1) != 0
+    order = np.argsort(-s.astype(np.float64), kind="stable")
+    ss, ts = s[order], t[order]
+    ends = np.nonzero(np.append(ss[1:] != ss[:-1], True))[0]
+    tp = np.cumsum(ts.astype(np.int64))[ends]
+    fp = (ends + 1) - tp
+    p_run = np.diff(tp, prepend=0)
+    q_run = np.diff(fp, prepend=0)
+    p, n = int(ts.sum()), int(s.size)
+    u = sum(int(a) * (2 * ((n - p) - int(b)) + int(c)) for a, b, c in zip(p_run, fp, q_run))
+    ap_num = float(np.sum(p_run.astype(np.float64) * (tp.astype(np.float64) / (tp + fp).astype(np.float64))))
+    return _ranking_from_sums(ap_num, u, p, n)

@@ -22,11 +22,12 @@ from . import engine as _engine
 from ._args import (MAX_CLASSES, _TARGET_KIND, _as_f32, _class_logits, _class_target, _flat, _ignore_args, _planes,  # noqa: F401
                     _require_cuda, _scalar)
 # every name that lived in this module before it was split stays importable from it
-from .losses import (MAX_SKELETON_ITERS, BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss, FocalLoss, SegLoss,  # noqa: F401
-                     TverskyLoss, _BCEFn, _CEFn, _check_iters, _clDiceFn, _FusedLossFn, _SegLossFn, _SoftSkeletonFn, _takes_fused_head,
+from .losses import (MAX_SKELETON_ITERS, BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss, FocalLoss, LovaszHingeLoss,  # noqa: F401
+                     SegLoss, TverskyLoss, _LovaszHingeFn, lovasz_hinge_reference, _BCEFn, _CEFn, _check_iters, _clDiceFn, _FusedLossFn, _SegLossFn, _SoftSkeletonFn, _takes_fused_head,
                      clDiceLoss, soft_skeleton)
 from .metrics import (PRCurve, SegConfusion, SegCounts, _confusion_pass, _split_counts, _StepConfusion, _StepCounts,  # noqa: F401
-                      argmax_classes, average_precision, best_dice_threshold, metrics_from_counts, multiclass_metrics_from_confusion)
+                      argmax_classes, average_precision, best_dice_threshold, metrics_from_counts, multiclass_metrics_from_confusion,
+                      ranking_metrics, ranking_reference, sort_scores)
 from .optim import FusedAdam, FusedSGD, _ptr_array  # noqa: F401
 
 

@@ -988,6 +988,49 @@ int hpri_cldice_bwd(const float* logits, const float* target, const float* p, co
 int hpri_centerline_counts(const unsigned char* skel_pred, const unsigned char* skel_truth, const unsigned char* pred,
                            const unsigned char* truth, int N, long long per_image, int* counts, hipStream_t stream);
 
+/* ---- device sort, the Lovasz hinge and the ranking metrics (sort.hip; hyperpri_amd/losses.py, metrics.py) --------------------------
+ *   hpri_sort_keys_f32      G groups of L fp32 keys, contiguous (G, L): perm[g][r] = the index inside group g of the key of rank r,
+ *                           bit for bit the indices of torch.sort(keys[g], descending, stable=True): by numeric value, NaN above
+ *                           +inf, -0.0 equal to +0.0, denormals in their order, ties in ascending index order; descending == 0:
+ *                           ascending (NaN last).  sorted_keys != NULL: also the keys in that order, their original bits gathered
+ *                           through perm.  A stable LSD radix sort, four 8-bit digits of an order-preserving uint32: a histogram
+ *                           launch, then per digit count / scan / scatter launches over tiles of hpri_sort_tile keys and a final
+ *                           gather -- 15 launches with the clearing of the histograms, for every size.  The rank inside a tile comes
+ *                           from wave ballots and a fixed scan, never from the order in which atomics land: bit-reproducible.  A
+ *                           digit that is the same in all keys of a group is skipped by the workgroups themselves (no host read).
+ *                           The only synchronisation between workgroups is the kernel boundary.  1 <= G <= 65535, L >= 1,
+ *                           G * L < 2^31; workspace: hpri_sort_workspace_bytes(G, L) bytes, 16-byte aligned.
+ *   hpri_lovasz_hinge_fwd   the Lovasz hinge (Berman et al., CVPR 2018) of fp32 logits and a fp32 target, N images of per_image
+ *                           pixels; a group is an image (per_image_groups != 0) or the batch.  s = target >= 0.5 ? +1 : -1,
+ *                           e = 1 - logit * s (fp32), the group's pixels in the order of e descending (the sort above), G1 = the
+ *                           group's positives, at rank r: P_r = positives among ranks 0 .. r, I_r = G1 - P_r, U_r = G1 + r + 1 - P_r,
+ *                           w_r = 1 / U_r for a positive and I_r / ((U_r - 1) U_r) for a negative pixel (G1 == 0: w_0 = 1, else 0),
+ *                           in fp64 from the integer counts; loss[0] = mean over the groups of sum_r relu(e_r) w_r (fp64 partial
+ *                           sums in a fixed order); coef[i] = -s_i w_rank(i) / groups where e_i > 0 and 0 elsewhere, rounded once.
+ *                           use_ignore != 0: pixels whose target equals ignore_index count for nothing (a group without any other
+ *                           pixel contributes 0).  17 launches, no host synchronisation.  workspace:
+ *                           hpri_lovasz_hinge_workspace_bytes(N, per_image, per_image_groups) bytes, 16-byte aligned.
+ *   hpri_lovasz_hinge_bwd   dlogits[i] = coef[i] * grad_out[0] (grad_out: device scalar, NULL = 1): one launch.
+ *   hpri_ranking_sums       one descending sort of n scores, then over the runs of equal scores (tp, fp: the positives and negatives
+ *                           down to the end of a run, p_run and q_run: those of the run; target_kind 0: fp32, 1: uint8, non-zero
+ *                           = positive): out[0] = the bits of the fp64 sum of p_run tp / (tp + fp) (average precision times the
+ *                           positives P), out[1] = the sum of p_run (2 (N - fp) + q_run) (ROC AUC times 2 P N, N the negatives:
+ *                           Mann-Whitney with ties counted half, an exact integer), out[2] = P.  17 launches.  workspace:
+ *                           hpri_ranking_workspace_bytes(n) bytes, 16-byte aligned; n < 2^31.
+ * The size functions and hpri_sort_tile are pure host functions (0 for sizes outside the limits).  A null pointer or a size outside the
+ * limits returns -1, a workspace that is too small -3, both before any launch. */
+int hpri_sort_tile(void);
+size_t hpri_sort_workspace_bytes(int G, int L);
+int hpri_sort_keys_f32(const float* keys, int G, int L, int descending, int* perm, float* sorted_keys, void* workspace,
+                       size_t workspace_bytes, hipStream_t stream);
+size_t hpri_lovasz_hinge_workspace_bytes(int N, long long per_image, int per_image_groups);
+int hpri_lovasz_hinge_fwd(const float* logits, const float* target, int N, long long per_image, int per_image_groups, int use_ignore,
+                          int ignore_index, float* loss, float* coef, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int hpri_lovasz_hinge_bwd(const float* coef, long long n, const float* grad_out, float* dlogits, hipStream_t stream);
+size_t hpri_ranking_workspace_bytes(long long n);
+int hpri_ranking_sums(const float* scores, const void* target, int target_kind, long long n, unsigned long long* out, void* workspace,
+                      size_t workspace_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
