@@ -11,6 +11,8 @@ import subprocess
 import pytest
 import torch
 
+from _persistent_cases import _Queue
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,35 +30,6 @@ def P(t):
 def lib():
     from hyperpri_amd import _lib
     return _lib.load()
-
-
-class _Queue:
-    """A caller-owned queue on a stream of its own (so that nothing else in the test process shares its registration)."""
-
-    def __init__(self, lib):
-        self.lib = lib
-        self.stream = torch.cuda.Stream(device=DEV)
-        self.h = ctypes.c_void_p(self.stream.cuda_stream)
-        self.buf = torch.zeros(lib.hpri_item_queue_bytes() // 4, dtype=torch.int32, device=DEV)
-        torch.cuda.synchronize()
-
-    def on(self):
-        assert self.lib.hpri_set_item_queue(P(self.buf), self.buf.numel() * 4, self.h) == 0, self.lib.hpri_last_error()
-        self.launches = 0                   # (registration resets the parity: the first launch draws from half 0)
-
-    def next_half_is_zero(self, taken=True):
-        """After a launch: the half the NEXT launch will draw from has been zeroed, the one just used holds its tickets.
-        ``taken=False``: a launch whose workgroups have one item each keeps its fixed lists and leaves the queue alone."""
-        if not taken:
-            return int(self.buf.abs().sum()) == 0
-        self.launches += 1
-        h = self.buf.numel() // 2
-        nxt = self.buf[:h] if self.launches % 2 == 0 else self.buf[h:]
-        used = self.buf[h:] if self.launches % 2 == 0 else self.buf[:h]
-        return int(nxt.abs().sum()) == 0 and int(used.abs().sum()) > 0
-
-    def off(self):
-        assert self.lib.hpri_set_item_queue(ctypes.c_void_p(0), 0, self.h) == 0
 
 
 @pytest.fixture
