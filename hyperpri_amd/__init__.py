@@ -15,7 +15,7 @@ from .distance import (boundary_reference, centerline_counts, centerline_from_co
                        surface_hist_reference, surface_metrics_from_hist, thin_reference)
 from .evaluate import (CLEAN_LOGIT, SplitPrediction, centerline_metrics, clean_prediction, cluster_split, color_classmaps, color_segmaps,  # noqa: F401
                        default_class_palette, detect_split, evaluate_multiclass, object_metrics, predict_split, surface_metrics, test_net, tta_merge,
-                       validate_net, write_segmaps, write_spreadmaps)
+                       unmix_split, validate_net, write_segmaps, write_spreadmaps)
 from .evaluate import root_traits as split_root_traits  # noqa: F401  (``root_traits`` is the per-tensor call of distance.py)
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
@@ -27,6 +27,7 @@ from .trainer import (BCEWithLogitsLoss, CrossEntropyLoss, DiceBCELoss, DiceLoss
                       LovaszHingeLoss, PRCurve, SegConfusion, SegCounts, SegLoss, SegmentationModel, TverskyLoss, argmax_classes,
                       average_precision, clDiceLoss, load_checkpoint, lovasz_hinge_reference, multiclass_metrics_from_confusion,
                       network_state_dict, ranking_metrics, ranking_reference, soft_skeleton, sort_scores)
+from .unmix import (SpectralUnmixer, atgp_reference, extract_endmembers, unmix_bound, unmix_bruteforce, unmix_reference)  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -290,6 +290,34 @@ def cluster_split(model: nn.Module, batches: Iterable[dict]) -> SplitPrediction:
         return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
 
 
+def unmix_split(model: nn.Module, batches: Iterable[dict], mode: str = "fcls") -> SplitPrediction:
+    """``cluster_split`` for an unmixer (``hyperpri_amd.SpectralUnmixer`` with a foreground endmember): per batch the model's ``"logit"``
+    map under ``mode`` -- the logit of every pixel's foreground abundance -- is stored as ``logits``, with masks, offsets, sizes and
+    names exactly as ``predict_split`` stores them, so the evaluation functions read a soft baseline unchanged."""
+    logits: List[torch.Tensor] = []
+    masks: List[torch.Tensor] = []
+    offsets, sizes, names = [0], [], []
+    with torch.inference_mode():
+        for batch in batches:
+            image, mask = batch["image"], batch["mask"]
+            _require_cuda(image, "evaluation image")
+            _require_device(mask, "evaluation mask")
+            pred = model(image, mode=mode, output="logit")[:, 0]
+            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
+            if mask.numel() != n * h * w:
+                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
+                                 f"and a mask {tuple(mask.shape)}")
+            logits.append(pred.reshape(-1).clone())
+            masks.append(mask.to(torch.float32).reshape(-1).clone())
+            names.extend(_names(batch.get("index"), n))
+            for _ in range(n):
+                offsets.append(offsets[-1] + h * w)
+                sizes.append((h, w))
+        if not logits:
+            raise ValueError("unmix_split: no batches")
+        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+
+
 def _bce(logits: torch.Tensor, masks: torch.Tensor) -> float:
     n = logits.numel()
     nws = _lib.load().hpri_bce_workspace_doubles(n)

@@ -940,6 +940,53 @@ int hpri_band_cluster_sums(const void* cache, int cache_dtype, int slots, int Hs
                            void* workspace, size_t workspace_bytes, long long* counts, double* sums, double* totals,
                            hipStream_t stream);
 
+/* ---- spectral unmixing: abundance maps and ATGP endmembers (unmix.hip; hyperpri_amd/unmix.py) ------------------------------------
+ * The linear mixing model x ~ E a with M <= hpri_band_unmix_max_members (8) endmembers E (C, M).  The host fits in fp64 and rounds
+ * once: E = Q R, the thin QR with a positive diagonal of R.  x: the zero-padded channels-last fp32 batch (pixels, cs) of
+ * hpri_band_detect (cs % 8 == 0, cs <= hpri_band_max_cs); basis: the rows of Q^T as fp32, zero-padded to (16, cs); members: E^T as fp32,
+ * (M, cs) with zero pad columns; tri: 2 M M doubles, R (row-major, upper triangular) and then G = R^T R.  Per pixel
+ *   1. y[m] = fmaf(basis[m][cs-1], x[cs-1], ... fmaf(basis[m][0], x[0], 0)), m < M   (v_mfma_f32_16x16x4_f32: bitwise this chain)
+ *   2. in fp64: b = R^T y, and a minimises |y - R a|^2 = 2 (1/2 a^T G a - b^T a) + |y|^2 under the mode
+ *        0 ucls  no constraint: G a = b, one Cholesky solve
+ *        1 scls  sum a = 1:  a = u - lambda v,  G u = b,  G v = 1,  lambda = (sum u - 1) / sum v
+ *        2 ncls  a >= 0            3 fcls  both
+ *      Modes 2 and 3: the active-set rule of Lawson and Hanson with the equality carried through.
+ *        start     ncls: S = {}, a = 0.  fcls: S = {j}, a = e_j, j = argmax_m (b[m] - G[m][m] / 2), the lowest index of a tie.
+ *        sub-solve s = the minimiser on the support S, zero elsewhere (fcls: with lambda from the two solves above restricted to S;
+ *                  ncls: lambda = 0).  A variable outside S has the identity's row and column and a zero right-hand side.
+ *        feasible  (s[i] > 0 for every i in S): a = s, w = b - G a - lambda, j = argmax over i not in S of w[i] (the lowest index of
+ *                  a tie); stop unless w[j] > tau = 2^-40 max_m G[m][m] max(1, max_m |y[m]|); else j joins S.
+ *        otherwise alpha = min over {i in S: s[i] <= 0} of a[i] / (a[i] - s[i]) (0 where a[i] == 0); a <- a + alpha (s - a); every i
+ *                  that attains alpha, and every i whose a[i] is not positive afterwards, leaves S and is set to exactly 0.
+ *        cap       at most `cap` sub-solves (0: 3 M).  A pixel that would need another keeps its current feasible a and adds one to
+ *                  capped[0] (unsigned 64-bit, ACCUMULATED with integer atomics; capped: 4 words, the others are left alone).
+ *   3. abundances[m * pixels + p] = (float) a[m]: M planes.
+ *   4. rmse (pixels), may be NULL: r[c] = fmaf(-members[M-1][c], a32[M-1], ... fmaf(-members[0][c], a32[0], x[c])) from the rounded
+ *      abundances, s = fmaf(r[c], r[c], s) from 0, ascending c over cs, rmse = sqrtf(s / C).
+ *   5. value (pixels), may be NULL: log(p) - log1p(-p) of p = clamp(f, 2^-24, 1 - 2^-24), f the fp32 sum, ascending m from 0, of a32[m]
+ *      over the members whose bit is set in `foreground` (the clamp and the logit of hpri_band_detect).
+ * No floating-point atomic; the result of a pixel depends neither on the pixel count, nor on the grid, nor on its place in a tile:
+ * identical arguments give identical bits.
+ *   hpri_band_extreme  one step of ATGP over the selected pixels of the listed slots (the leading arguments of hpri_band_gram, fp32
+ *                      and fp16 caches).  basis: K <= 8 orthonormal fp32 rows, zero-padded to (16, cs) (may be NULL with K == 0).  Per
+ *                      pixel y[k] as in 1., r[c] = fmaf(-basis[K-1][c], y[K-1], ... fmaf(-basis[0][c], y[0], x[c])), v = fmaf(r[c],
+ *                      r[c], v) from 0, ascending c over cs (K == 0: the squared norm).  value[0] = the largest v, position[0] = e *
+ *                      Hs * Ws + the pixel inside the slot, e the list entry; between equal v the lowest position; -1 when no pixel
+ *                      is selected (a NaN never wins).  Per-workgroup (v, position) partials in the workspace, then one fixed-order
+ *                      pick by the same total order: the result does not depend on the grid.  workspace:
+ *                      hpri_band_extreme_workspace_bytes() bytes, 16-byte aligned; a pure host query, a constant.
+ * Argument errors (a null pointer, a size <= 0, cs % 8 != 0 or beyond hpri_band_max_cs, M outside [1, 8], C outside [M, cs], a mode
+ * outside [0, 3], a negative cap, a foreground bit beyond M, K outside [0, 8], a select or dtype out of range, a selection without
+ * masks, a workspace that is too small, a misaligned pointer) return -1 before any launch. */
+int hpri_band_unmix_max_members(void);
+int hpri_band_unmix(const float* x, long long pixels, int cs, int C, const float* basis, const float* members, const double* tri,
+                    int M, int mode, int cap, int foreground, float* abundances, float* rmse, float* value,
+                    unsigned long long* capped, hipStream_t stream);
+size_t hpri_band_extreme_workspace_bytes(void);
+int hpri_band_extreme(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const unsigned char* masks,
+                      const int* slot_table, int n, int select, const float* basis, int K, void* workspace, size_t workspace_bytes,
+                      float* value, long long* position, hipStream_t stream);
+
 /* ---- soft skeletons and the centerline loss clDice (skeleton.hip; hyperpri_amd/trainer.py, distance.py) ------------------------
  * fp32 planes (N, h, w), contiguous, values meant to lie in [0, 1]; 0 <= iters <= hpri_soft_skeleton_max_iters (32).
  *   E(I)[u] = min over the in-image part of the plus neighbourhood {N, W, C, E, S} of u,  D(I)[u] = max over the in-image 3x3
