@@ -131,3 +131,19 @@ def _class_target(target: torch.Tensor, x: torch.Tensor, what: str) -> torch.Ten
 
 def _ignore_args(ignore_index: Optional[int]) -> Tuple[int, int]:
     return (0, 0) if ignore_index is None else (1, int(ignore_index))
+
+
+FILTER_DOMAINS = ("linear", "prob")
+
+
+def _filter_args(radius, eps, domain, max_radius: int, who: str) -> Tuple[int, float, int]:
+    """The parameters of an edge-preserving filter as its kernels take them: (radius in [1, max_radius], eps as the fp32 value the
+    launch receives -- positive and finite --, the code of ``domain``)."""
+    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= max_radius:
+        raise ValueError(f"{who}: radius must be an integer in [1, {max_radius}], got {radius!r}")
+    e = float(np.float32(_scalar(eps, f"{who}: eps")))
+    if not (e > 0.0 and np.isfinite(e)):
+        raise ValueError(f"{who}: eps must be positive and finite as an fp32 value, got {eps!r}")
+    if domain not in FILTER_DOMAINS:
+        raise ValueError(f"{who}: domain must be one of {FILTER_DOMAINS}, got {domain!r}")
+    return int(radius), e, FILTER_DOMAINS.index(domain)

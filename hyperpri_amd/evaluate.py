@@ -318,6 +318,36 @@ def unmix_split(model: nn.Module, batches: Iterable[dict], mode: str = "fcls") -
         return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
 
 
+def refine_split(pred: SplitPrediction, batches: Iterable[dict], guide, radius: int, eps: float, domain: str = "prob") -> SplitPrediction:
+    """Edge-preserving refinement of a stored split (``hyperpri_amd.guided_filter``, ``csrc/guided.hip``): ``batches`` serves the split
+    once more in the order it was predicted in, as for ``write_segmaps``; per batch ``guide(batch["image"])`` -- a
+    ``SpectralProjection`` with at most three outputs, or any callable that returns ``(N, K, h, w)`` (or ``(N, 1, K, h, w)``) with
+    K <= 3 -- guides the filter over the stored logits (``domain="prob"``: filtered as probabilities, stored as logits again).
+    Returns a new ``SplitPrediction`` with the filtered logits and the same masks, offsets, sizes and names; ``spread`` is carried
+    over.  ``validate_net``, ``test_net``, ``clean_prediction``, ``surface_metrics`` and ``write_segmaps`` read it unchanged."""
+    from .guided import MAX_GUIDES, guided_filter
+    if getattr(guide, "out_channels", 0) > MAX_GUIDES:
+        raise ValueError(f"refine_split: the guide has {guide.out_channels} outputs, the filter takes at most {MAX_GUIDES}")
+    logits: List[torch.Tensor] = []
+    i = 0
+    with torch.inference_mode():
+        for batch in batches:
+            image = batch["image"]
+            _require_cuda(image, "evaluation image")
+            n, (h, w) = int(image.shape[0]), (int(image.shape[-2]), int(image.shape[-1]))
+            if i + n > len(pred):
+                raise ValueError("refine_split: the batches hold more images than the stored prediction")
+            if _names(batch.get("index"), n) != pred.names[i:i + n] or any(s != (h, w) for s in pred.sizes[i:i + n]):
+                raise ValueError(f"refine_split: images {i}..{i + n - 1} are not the ones the prediction stored (serve the split in "
+                                 "the same order, unshuffled)")
+            a, b = pred.offsets[i], pred.offsets[i + n]
+            logits.append(guided_filter(guide(image), pred.logits[a:b].view(n, h, w), radius, eps, domain).reshape(-1))
+            i += n
+    if i != len(pred):
+        raise ValueError(f"refine_split: the batches held {i} of the {len(pred)} stored images")
+    return SplitPrediction(torch.cat(logits), pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
+
+
 def _bce(logits: torch.Tensor, masks: torch.Tensor) -> float:
     n = logits.numel()
     nws = _lib.load().hpri_bce_workspace_doubles(n)

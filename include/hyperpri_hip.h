@@ -987,6 +987,46 @@ int hpri_band_extreme(const void* cache, int cache_dtype, int slots, int Hs, int
                       const int* slot_table, int n, int select, const float* basis, int K, void* workspace, size_t workspace_bytes,
                       float* value, long long* position, hipStream_t stream);
 
+/* ---- guided filter: edge-preserving smoothing of score maps (guided.hip; hyperpri_amd/guided.py) ----------------------------------
+ * The guided filter of He, Sun and Tang with a K-channel guide, 1 <= K <= hpri_guided_max_guides (3), for T >= 1 maps on one frame.
+ * guide: fp32 channels-last (N, H, W, gs), K <= gs; the first K channels are read (gs = 1: a plain plane; a 16-byte aligned buffer with
+ * gs % 4 == 0 is read in quads).  maps and out: fp32 planes (N, T, H, W).  1 <= radius <= hpri_guided_max_radius (8), eps > 0 (an fp32
+ * value, used as a double).  The window of a pixel is the (2 radius + 1)^2 square clipped to the image, n the number of its in-image
+ * pixels; nothing outside the image contributes.  Every window is walked row by row, its pixels inside a row from left to right.
+ *   hpri_guided_coeffs  stage 1, per pixel k and map, centred on k itself so that no mean is subtracted from a moment:
+ *       dI_j[a] = I_j[a] - I_k[a],  dp_j = p_j - p_k                                            fp32, j over the window of k
+ *       S1[a] += dI_j[a],  S2[a][b] = fmaf(dI_j[a], dI_j[b], S2[a][b]) (a <= b),  s += dp_j,  Sp[a] = fmaf(dI_j[a], dp_j, Sp[a])
+ *                                                                                               fp32 from 0, in the window's order
+ *       in fp64, no contraction: m[a] = S1[a] / n;  A[a][b] = S2[a][b] / n - m[a] m[b], plus eps on the diagonal;  sn = s / n;
+ *       c[a] = Sp[a] / n - m[a] sn;  a = A^-1 c.  K = 1: a = c / A, one division.  K > 1: the Cholesky factor column by column
+ *       (L[j][j] = sqrt(A[j][j] - L[j][0]^2 - ...), L[i][j] = (A[i][j] - L[i][0] L[j][0] - ...) / L[j][j], subtractions in ascending
+ *       order), z[i] = (c[i] - L[i][0] z[0] - ...) / L[i][i] ascending i, then a[i] = (z[i] - L[i+1][i] a[i+1] - ...) / L[i][i]
+ *       descending i.
+ *       workspace, fp32 (N, T, 2K+1, H, W):  planes 0 .. K-1: a;  K .. 2K-1: mI[a] = I_k[a] + m[a];  2K: mp = p_k + sn; each the fp64
+ *       value rounded once.  A and mI do not depend on the map; a map's planes do not depend on T.
+ *   hpri_guided_apply   stage 2, per pixel i and map:  t_k = fmaf(a_k[K-1], I_i[K-1] - mI_k[K-1], ... fmaf(a_k[0], I_i[0] - mI_k[0],
+ *       mp_k)),  q = (t_k summed in fp32 from 0 over the window of i, in its order) / (float) n.  (The line through the window's own
+ *       mean, never mean(a) . I + mean(b): the same reason as the centring.)
+ *   domain 0 (linear): maps are taken and written as they are.  domain 1 (prob): stage 1 reads p = sigmoid(z) of the stored logits z
+ *       (1 / (1 + exp(-|z|)), or exp(-|z|) times that for z < 0), stage 2 writes log(c) - log1p(-c) of c = clamp(q, 2^-24, 1 - 2^-24),
+ *       the clamp and the logit of hpri_band_detect and hpri_band_unmix.
+ * Both launches work on tiles of hpri_guided_tile_h x hpri_guided_tile_w pixels with a halo of radius in LDS, one lane a pixel; stage 1
+ * takes the maps in groups of four.  No atomics: the result of a pixel depends on its neighbourhood and its distance to the image
+ * borders, not on N, T, the grid or its place in a tile; identical arguments give identical bits.
+ * workspace: hpri_guided_workspace_bytes(N, T, H, W, K) = 4 N T (2K+1) H W bytes (0 for sizes outside the limits: H W < 2^31,
+ * N T H W < 2^40), 4-byte aligned; a pure host query.  Argument errors (a null pointer, a size < 1, K outside [1, 3], gs < K, a radius
+ * outside [1, 8], eps not positive and finite, a domain other than 0 or 1, a workspace that is too small, a misaligned pointer) return
+ * -1 before any launch. */
+int hpri_guided_max_radius(void);
+int hpri_guided_max_guides(void);
+int hpri_guided_tile_h(void);
+int hpri_guided_tile_w(void);
+size_t hpri_guided_workspace_bytes(int N, int T, int H, int W, int K);
+int hpri_guided_coeffs(const float* guide, int gs, int K, const float* maps, int N, int T, int H, int W, int radius, float eps,
+                       int domain, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int hpri_guided_apply(const float* guide, int gs, int K, int N, int T, int H, int W, int radius, int domain, const void* workspace,
+                      size_t workspace_bytes, float* out, hipStream_t stream);
+
 /* ---- soft skeletons and the centerline loss clDice (skeleton.hip; hyperpri_amd/trainer.py, distance.py) ------------------------
  * fp32 planes (N, h, w), contiguous, values meant to lie in [0, 1]; 0 <= iters <= hpri_soft_skeleton_max_iters (32).
  *   E(I)[u] = min over the in-image part of the plus neighbourhood {N, W, C, E, S} of u,  D(I)[u] = max over the in-image 3x3
