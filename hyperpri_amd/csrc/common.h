@@ -101,8 +101,8 @@ typedef unsigned hpri_u32x4 __attribute__((ext_vector_type(4)));
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(hpri_u32x4, v_), rs_, voff_, soff_, 0)
 #else
 typedef int hpri_rsrc_t;
-#define HPRI_MAKE_RSRC(ptr_, bytes_) 0
-#define HPRI_LDS_DMA16(rs_, lds_, voff_, soff_) ((void)(rs_))
+#define HPRI_MAKE_RSRC(ptr_, bytes_) ((void)(ptr_), (void)(bytes_), 0)
+#define HPRI_LDS_DMA16(rs_, lds_, voff_, soff_) ((void)(rs_), (void)(lds_), (void)(voff_), (void)(soff_))
 #define HPRI_BUFFER_LOAD_F32(rs_, voff_, soff_) 0.f
 #define HPRI_BUFFER_LOAD_F32X4(rs_, voff_, soff_) (f32x4{0.f, 0.f, 0.f, 0.f})
 #define HPRI_BUFFER_STORE_F32X4(v_, rs_, voff_, soff_) ((void)(rs_))

@@ -85,40 +85,89 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
   // buffer_load ... lds: the descriptor base is the unit's first (halo) pixel -- a wave-uniform pointer that may lie before the
   // tensor for border units --, the piece's row / pixel-group offset goes in as the scalar offset, and the lane part is ONE
   // per-lane constant; lanes outside the image, beyond the valid channels or in the unused tail of a staged row get an
-  // out-of-range offset, which the hardware range check turns into zeros in LDS (tools/lds_dma_oob.hip).  About 4 vector
-  // instructions per piece instead of ~20 (every one of them costs fp32-MFMA issue time).
-  constexpr int NPX = 4 * (WG_XROW / 4), NPY = 2 * 8, NPW = (NPX + NPY + 7) / 8;
+  // out-of-range offset, which the hardware range check turns into zeros in LDS (tools/lds_dma_oob.hip).
+  // NOTHING of that is worked out per unit (before: ~150 scalar and ~45 vector instructions and 7 s_nop 4 per wave between a
+  // unit's barrier and its first MFMA, with all eight waves of the CU -- one workgroup, no partner -- issuing at once and every
+  // matrix pipe idle meanwhile; profiles/wgrad_units_isa_census.json):
+  //   piece      wave, piece index, row, pixel group, LDS destination: compile-time per wave variant; the scalar offset
+  //              (row * W + pixel group) * cs * 4: one SGPR per piece, set before the unit loop
+  //   lanes      one offset register per piece and strip-COLUMN CLASS -- first (pixel -1 is left of the image), middle (every
+  //              pixel of the strip and its halo is inside), last (hangs over the right edge; with one strip per row it is also
+  //              the first and its offsets say so) -- with channel validity and the tail of a staged row folded in; a unit
+  //              picks the class by a wave-uniform branch, no lane compares
+  //   rows       a row above or below the image (or the second dY row of an odd H) is wave-uniform: its pieces go through a
+  //              descriptor of ZERO records, so every lane is out of range whatever its offset
+  //   pointers   the two base pointers are carried from unit to unit by one of three constant steps (next strip, next strip
+  //              row, next image); what describes a unit (class, record counts, pointers, k-steps) is prepared one unit ahead
+  //   issue      the pieces of unit u + 1 go into the gaps between the 8 MFMAs of unit u's FIRST k-step (peeled out of the
+  //              runtime-trip loop: every unit has one); its buffer is free from the barrier at the top of unit u on
+    constexpr int NPX = 4 * (WG_XROW / 4), NPY = 2 * 8, NPW = (NPX + NPY + 7) / 8;
   constexpr unsigned OOB = 0xFFFFFFF0u;
+  constexpr int NREC = 0x7FFFFF00;
   const int l4 = lane >> 4;                          // pixel of the piece's group of four
   const unsigned xlane = (c_blk + (lane & 15) * 4 < a.x_cvalid) ? (unsigned)(l4 * a.x_cs * 4 + (lane & 15) * 16) : OOB;
   const unsigned ylane = (n_blk + (lane & 15) * 4 < a.dy_cvalid) ? (unsigned)(l4 * a.dy_cs * 4 + (lane & 15) * 16) : OOB;
-  // units are loaded in order, u0, u0 + 1, ...: the (strip column, strip row, image) of the next one is carried along and
-  // wrapped, not divided out of the unit index every time
-  int ld_sx = u0 % a.strips_x, ld_sy = (u0 / a.strips_x) % a.strips_y, ld_img = u0 / (a.strips_x * a.strips_y);
-#define LOAD_UNIT(buf_)                                                                                                \
+  const unsigned xfirst = l4 >= 1 ? xlane : OOB;     // first column class, pixel group 0: pixel -1
+  const unsigned xtail = l4 < 2 ? xlane : OOB;       // pixel group 32: halo pixels 32, 33 of the 36 staged
+  const int sxl = a.strips_x - 1, syl = a.strips_y - 1, x0l = sxl * 32;
+  const int kend_last = min(8, (a.kw - x0l + 3) >> 2);          // k-steps of the last strip of a strip row (wave-uniform)
+  // units are loaded in order, u0, u0 + 1, ...: the (strip column, strip row) of the next one and its two base pointers are
+  // carried along and wrapped, not divided or multiplied out of the unit index every time
+  int ld_sx = u0 % a.strips_x, ld_sy = (u0 / a.strips_x) % a.strips_y;
+  const char *ld_x, *ld_y;
+  {
+    const int img_ = u0 / (a.strips_x * a.strips_y), y0_ = ld_sy * 2, x0_ = ld_sx * 32;
+    ld_x = (const char*)(a.x + ((long long)(img_ * a.H + y0_ - 1) * a.W + x0_ - 1) * a.x_cs + a.x_coff + c_blk);
+    ld_y = (const char*)(a.dy + ((long long)(img_ * a.H + y0_) * a.W + x0_) * a.dy_cs + a.dy_coff + n_blk);
+  }
+  // pixels from a unit's first pixel to the next unit's: next strip | next strip row | first strip row of the next image
+  const int px_row = 2 * a.W - x0l, px_img = (a.H - 2 * syl) * a.W - x0l;
+  const int xd_step = 32 * a.x_cs * 4, xd_row = px_row * a.x_cs * 4, xd_img = px_img * a.x_cs * 4;
+  const int yd_step = 32 * a.dy_cs * 4, yd_row = px_row * a.dy_cs * 4, yd_img = px_img * a.dy_cs * 4;
+  // the unit that is loaded next, prepared one unit ahead (WG_PREPARE): column class 0 first | 1 middle | 2 last, the records of
+  // the descriptors of halo row 0, of halo row 3, and of halo row 2 = dY row 1, base pointers, k-steps
+  int pr_cls, pr_top, pr_bot, pr_bot1, pr_kend;
+  const char *pr_x, *pr_y;
+#define WG_PREPARE                                                                                                     \
   {                                                                                                                    \
-    const int sx_ = ld_sx, sy_ = ld_sy, img_ = ld_img;                                                                 \
-    if (++ld_sx == a.strips_x) { ld_sx = 0; if (++ld_sy == a.strips_y) { ld_sy = 0; ++ld_img; } }                      \
-    const int y0_ = sy_ * 2, x0_ = sx_ * 32;                                                                           \
-    kend_next = min(8, (a.kw - x0_ + 3) >> 2);                /* k-steps of this unit (wave-uniform) */                \
-    unsigned char* lb_ = smem + (buf_) * WG_STAGE_BYTES;                                                               \
-    const float* xu_ = a.x + ((long long)(img_ * a.H + y0_ - 1) * a.W + x0_ - 1) * a.x_cs + a.x_coff + c_blk;          \
-    const float* yu_ = a.dy + ((long long)(img_ * a.H + y0_) * a.W + x0_) * a.dy_cs + a.dy_coff + n_blk;               \
-    const hpri_rsrc_t rx_ = HPRI_MAKE_RSRC(xu_, 0x7FFFFF00);       \
-    const hpri_rsrc_t ry_ = HPRI_MAKE_RSRC(yu_, 0x7FFFFF00);       \
-    _Pragma("unroll") for (int p = 0; p < NPW; ++p) {                                                                  \
-      const int piece_ = p * 8 + wave;                                                                                 \
-      if (piece_ < NPX) {                                                                                              \
-        const int row_ = piece_ / (WG_XROW / 4), pxb_ = (piece_ % (WG_XROW / 4)) * 4;          /* wave-uniform */       \
-        const bool rowok_ = (unsigned)(y0_ + row_ - 1) < (unsigned)a.H;                                                \
-        const bool ok_ = rowok_ && (pxb_ + l4) < 34 && (unsigned)(x0_ + pxb_ + l4 - 1) < (unsigned)a.W;                \
-        HPRI_LDS_DMA16(rx_, lb_ + piece_ * 1024, ok_ ? xlane : OOB, (row_ * a.W + pxb_) * a.x_cs * 4);           \
-      } else if (piece_ < NPX + NPY) {                                                                                 \
-        const int pp_ = piece_ - NPX;                                                                                  \
-        const int row_ = pp_ >> 3, pxb_ = (pp_ & 7) * 4;                                                               \
-        const bool ok_ = (y0_ + row_) < a.H && (x0_ + pxb_ + l4) < a.W;                                                \
-        HPRI_LDS_DMA16(ry_, lb_ + piece_ * 1024, ok_ ? ylane : OOB, (row_ * a.W + pxb_) * a.dy_cs * 4);          \
-      }                                                                                                                \
+    const bool lastx_ = ld_sx == sxl, lasty_ = ld_sy == syl;                                                           \
+    pr_cls = lastx_ ? 2 : min(ld_sx, 1);       /* (min: a select of a compare went through a vector register) */      \
+    pr_kend = lastx_ ? kend_last : 8;                                                                                  \
+    pr_top = ld_sy == 0 ? 0 : NREC;                                                                                    \
+    pr_bot = lasty_ ? 0 : NREC;                                                                                        \
+    pr_bot1 = (lasty_ && (a.H & 1)) ? 0 : NREC;                                                                        \
+    pr_x = ld_x; pr_y = ld_y;                                                                                          \
+    const int xd_ = lastx_ ? (lasty_ ? xd_img : xd_row) : xd_step, yd_ = lastx_ ? (lasty_ ? yd_img : yd_row) : yd_step; \
+    ld_x += xd_; ld_y += yd_;                                                                                          \
+    ld_sx = lastx_ ? 0 : ld_sx + 1;                                                                                    \
+    ld_sy = lastx_ ? (lasty_ ? 0 : ld_sy + 1) : ld_sy;                                                                 \
+  }
+// piece p_ of wave variant WV_ of the prepared unit, column class CLS_ (both compile-time), into stage buffer lb_
+#define WG_PIECE(p_, CLS_)                                                                                             \
+  if ((p_) * 8 + WV_ < NPX + NPY) {                                                                                    \
+    constexpr int piece_ = (p_) * 8 + WV_;                                                                             \
+    constexpr bool isx_ = piece_ < NPX;                                                                                \
+    constexpr int row_ = isx_ ? piece_ / (WG_XROW / 4) : (piece_ - NPX) >> 3;                                          \
+    constexpr int pxb_ = isx_ ? (piece_ % (WG_XROW / 4)) * 4 : ((piece_ - NPX) & 7) * 4;                               \
+    const unsigned vo_ = (CLS_) == 2 ? vlast[p_] : !isx_ ? ylane : pxb_ == 32 ? xtail : ((CLS_) == 0 && pxb_ == 0) ? xfirst : xlane; \
+    const int nrec_ = isx_ ? (row_ == 0 ? pr_top : row_ == 2 ? pr_bot1 : row_ == 3 ? pr_bot : NREC) : (row_ == 1 ? pr_bot1 : NREC); \
+    HPRI_LDS_DMA16(HPRI_MAKE_RSRC(isx_ ? pr_x : pr_y, nrec_), lb_ + piece_ * 1024, vo_, soff[p_]);                     \
+  }
+// the per-(wave, piece) constants: scalar offsets, and the lane offsets of the last column class (x0 = x0l; with one strip per
+// row the strip is also the first: the unsigned compare covers pixel -1)
+#define WG_PIECE_SETUP                                                                                                 \
+  int soff[NPW]; unsigned vlast[NPW];                                                                                  \
+  _Pragma("unroll") for (int p = 0; p < NPW; ++p) {                                                                    \
+    const int piece_ = p * 8 + WV_;                                                                                    \
+    soff[p] = 0; vlast[p] = OOB;                                                                                       \
+    if (piece_ < NPX) {                                                                                                \
+      const int row_ = piece_ / (WG_XROW / 4), pxb_ = (piece_ % (WG_XROW / 4)) * 4;                                    \
+      soff[p] = (row_ * a.W + pxb_) * a.x_cs * 4;                                                                      \
+      vlast[p] = ((pxb_ + l4) < 34 && (unsigned)(x0l + pxb_ + l4 - 1) < (unsigned)a.W) ? xlane : OOB;                  \
+    } else if (piece_ < NPX + NPY) {                                                                                   \
+      const int row_ = (piece_ - NPX) >> 3, pxb_ = ((piece_ - NPX) & 7) * 4;                                           \
+      soff[p] = (row_ * a.W + pxb_) * a.dy_cs * 4;                                                                     \
+      vlast[p] = (x0l + pxb_ + l4) < a.W ? ylane : OOB;                                                                \
     }                                                                                                                  \
   }
 
@@ -131,8 +180,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 // with or without an opaque lane id: rejected.  Two k-steps per trip plus a straight-line odd step measured no faster than
 // running all 8 (experiments/README.md).
 // Every vector or LDS instruction of the k-step is paid in matrix-pipe time, so the step holds the transform and
-// nothing else: 13 (rows 0, 3) or 17 (rows 1, 2) vector and 8 or 10 LDS instructions per 8 MFMAs, 159 registers
-// (profiles/wgrad_kstep_isa_census.json; before: 19-29 and 8-10, 185).
+// nothing else: 13 (rows 0, 3) or 17 (rows 1, 2) vector and 8 or 10 LDS instructions per 8 MFMAs
+// (profiles/wgrad_kstep_isa_census.json; before: 19-29 and 8-10); the kernel takes 164 registers (185 before the k-step was cut down).
 //   operands   lane li holds input channels 2 li, 2 li + 1 (its cin tiles ct = 0, 1) and output channels 2 li, 2 li + 1 (its cout
 //              tiles nt = 0, 1): both tiles' operands of a pixel are ONE ds_read_b64 (conflict-free: 32 lanes x 8 bytes are the
 //              pixel's 256 bytes).  Which channel sits in which MFMA row or column changes no sum; the slab write puts them back.
@@ -144,7 +193,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 //              signs s1 s2 are compile-time per variant: d1 + s1 s2 d2 is one add or one subtract, the same bits as the FMA.
 //   schedule   sched_barrier: operands first, then the 8 MFMAs back to back (left alone hipcc spread the transform between the
 //              MFMAs and re-used operand registers: 7-8 s_nop per k-step).
-#define K_STEP(FA_, FB_)                                      /* MFMA k-step kk: tiles 2 kk + lh of the strip */         \
+#define K_STEP(FA_, FB_, GAP_, END_)        /* MFMA k-step kk: tiles 2 kk + lh of the strip; what goes between its MFMAs */ \
     {                                                                                                                  \
       constexpr int R1_ = (FA_ == 0) ? 0 : 1, R2_ = (FA_ == 3) ? 3 : 2;             /* halo rows of the row transform */ \
       constexpr int YR_ = (FA_ == 3) ? 1 : 0, YROWS_ = (FA_ == 1 || FA_ == 2) ? 2 : 1;                                 \
@@ -188,23 +237,58 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
         vb[1][nt] = FB_ ? t[1][nt] : (t[0][nt] + t[1][nt]);                                                            \
                                                                                                                        \
       }                                                                                                                \
-      __builtin_amdgcn_sched_barrier(0);            /* operands first, then the 8 MFMAs back to back */                \
+      /* (volatile pins: the branches in the gaps of a unit's first k-step end the basic block, and hipcc sinks */     \
+      /* an operand's last subtract to its first use between the MFMAs otherwise, with an s_nop 1 each) */             \
       _Pragma("unroll") for (int e = 0; e < 2; ++e)                                                                    \
-          _Pragma("unroll") for (int ct = 0; ct < 2; ++ct)                                                             \
-              _Pragma("unroll") for (int nt = 0; nt < 2; ++nt)                                                         \
-                  acc[e][ct][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[e][ct], vb[e][nt], acc[e][ct][nt], 0, 0, 0); \
+        _Pragma("unroll") for (int q = 0; q < 2; ++q) { asm volatile("" : "+v"(va[e][q])); asm volatile("" : "+v"(vb[e][q])); } \
+      __builtin_amdgcn_sched_barrier(0);            /* operands first, then the 8 MFMAs back to back */                \
+      WG_MFMA(0, 0, 0) GAP_(0) WG_MFMA(0, 0, 1) GAP_(1) WG_MFMA(0, 1, 0) GAP_(2) WG_MFMA(0, 1, 1) GAP_(3)              \
+      WG_MFMA(1, 0, 0) GAP_(4) WG_MFMA(1, 0, 1) GAP_(5) WG_MFMA(1, 1, 0) GAP_(6) WG_MFMA(1, 1, 1) END_                 \
       kp += 1024;                                   /* four pixel columns on */                                        \
     }
-  // the variant is chosen once per wave, outside the unit loop (eight copies of the loop, no selects inside)
+#define WG_MFMA(e_, ct_, nt_) \
+  acc[e_][ct_][nt_] = __builtin_amdgcn_mfma_f32_32x32x2f32(va[e_][ct_], vb[e_][nt_], acc[e_][ct_][nt_], 0, 0, 0);
+  // the gaps of a unit's first k-step: piece i of the next unit behind MFMA i (6 or 7 pieces for 7 gaps), and behind the last
+  // MFMA the scalar work that describes the unit after that; sched_barrier keeps each where it stands
+#define WG_NOGAP(i_)
+#define WG_GAP(i_) __builtin_amdgcn_sched_barrier(0); WG_PIECE_IN_LOOP(i_) __builtin_amdgcn_sched_barrier(0);
+#define WG_END __builtin_amdgcn_sched_barrier(0); kend_next = pr_kend; WG_PREPARE
+  // the variant is chosen once per wave, outside the unit loop (eight copies of the loop, no selects inside); so are a wave's
+  // pieces.  A unit that has a successor runs its first k-step in the copy that issues the successor's pieces, the rest in the
+  // loop.  (One copy of that k-step per column class, each with its own MFMAs, spilled 252 bytes: the class branches lie in the gaps.)
 #define UNIT_LOOP(FA_, FB_)                                                                                            \
-  for (int u = u0; u < u1; ++u) {                                                                                      \
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                   \
-    __builtin_amdgcn_s_barrier();          /* this unit has landed for everyone; the other buffer is free */           \
-    const int kend = kend_next;                                                                                        \
-    if (u + 1 < u1) LOAD_UNIT((u + 1 - u0) & 1)                                                                         \
-    unsigned kp = ((u - u0) & 1) * WG_STAGE_BYTES + klane;                                                             \
-    for (int kk = 0; kk < kend; ++kk) K_STEP(FA_, FB_)                                                                 \
+  {                                                                                                                    \
+    constexpr int WV_ = 2 * FA_ + FB_;                                                                                 \
+    WG_PIECE_SETUP                                                                                                     \
+    if (u0 < u1) {                                                                                                     \
+      unsigned char* lb_ = smem;                                                                                       \
+      WG_PREPARE                                                                                                       \
+      kend_next = pr_kend;                                                                                             \
+      WG_PIECE_ANY(0) WG_PIECE_ANY(1) WG_PIECE_ANY(2) WG_PIECE_ANY(3) WG_PIECE_ANY(4) WG_PIECE_ANY(5) WG_PIECE_ANY(6)  \
+      WG_PREPARE                                                                                                       \
+    }                                                                                                                  \
+    for (int u = u0; u < u1; ++u) {                                                                                    \
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
+      __builtin_amdgcn_s_barrier();        /* this unit has landed for everyone; the other buffer is free */           \
+      const int kend = kend_next;                                                                                      \
+      unsigned kp = WG_BUF_OF(u - u0) * WG_STAGE_BYTES + klane;                                                        \
+      int kk = 0;                                                                                                      \
+      if (u + 1 < u1) {                                                                                                \
+        unsigned char* lb_ = smem + ((u + 1 - u0) & 1) * WG_STAGE_BYTES;                                               \
+        K_STEP(FA_, FB_, WG_GAP, WG_END)                                                                               \
+        kk = 1;                                                                                                        \
+      }                                                                                                                \
+      for (; kk < kend; ++kk) K_STEP(FA_, FB_, WG_NOGAP, )                                                             \
+    }                                                                                                                  \
   }
+// ... of the prepared unit's column class: a wave-uniform branch around the copies that differ (the first class differs from
+// the middle one in the pieces of pixel group 0 only).  The asm comments make the arms differ behind the load: hipcc otherwise
+// sinks the load below the branch and selects its lane offset per lane (v_cndmask) on a class it keeps in a vector register
+#define WG_PIECE_ANY(p_)                                                                                               \
+  if (pr_cls == 2) { WG_PIECE(p_, 2) asm volatile("; last column class"); }                                            \
+  else if (pr_cls == 0 && (p_) * 8 + WV_ < NPX && ((p_) * 8 + WV_) % (WG_XROW / 4) == 0) {                             \
+    WG_PIECE(p_, 0) asm volatile("; first column class");                                                              \
+  } else { WG_PIECE(p_, 1) asm volatile("; middle column class"); }
   const unsigned klane = (unsigned)(lh * 512 + li * 8);
   typedef __attribute__((address_space(3))) const unsigned char* wg_lds_bytes;
   typedef __attribute__((address_space(3))) const volatile f32x2* wg_lds_f32x2;
@@ -212,7 +296,15 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
 #define WG_LDS2(off_) (*(wg_lds_f32x2)(lds + (off_)))
 #define WG_PIN(v_) asm("" : "+v"(v_));
   int kend_next = 8;
-  if (u0 < u1) LOAD_UNIT(0)
+#ifdef WGRAD_DIAG_NO_UNIT_LOAD
+  // timing-only build (tools/build_wgrad_diag.sh): the unit loop issues no loads, every unit multiplies the first unit's data;
+  // results are meaningless, the time is what is left when loading the next unit costs nothing
+#define WG_PIECE_IN_LOOP(i_)
+#define WG_BUF_OF(i_) 0
+#else
+#define WG_PIECE_IN_LOOP(i_) WG_PIECE_ANY(i_)
+#define WG_BUF_OF(i_) ((i_) & 1)
+#endif
   switch (wave) {                          // wave = 2 fa + fb
     case 0: UNIT_LOOP(0, 0) break;
     case 1: UNIT_LOOP(0, 1) break;
@@ -225,7 +317,16 @@ __global__ __launch_bounds__(512, 2) void conv_wino_wgrad_kernel(WinoWgradArgs a
   }
 #undef UNIT_LOOP
 #undef K_STEP
-#undef LOAD_UNIT
+#undef WG_MFMA
+#undef WG_NOGAP
+#undef WG_GAP
+#undef WG_END
+#undef WG_PIECE_ANY
+#undef WG_PIECE_IN_LOOP
+#undef WG_PIECE
+#undef WG_PIECE_SETUP
+#undef WG_PREPARE
+#undef WG_BUF_OF
 #undef WG_LDS2
 #undef WG_PIN
   // slab: ws[split][xi][c][n]; accumulator rows = cin (register index), columns = cout (lane)

@@ -9,7 +9,8 @@ Second form, for a kernel with several k loops (conv_wino_wgrad_kernel: one per 
     isa_census.py --loops conv_wino.hip conv_wino_wgrad_kernel [mfmas_per_k_step] [--source FILE]
 lists every innermost single-block loop that holds an MFMA, in the order of the listing: MFMAs, vector instructions by mnemonic,
 LDS instructions by mnemonic, waits, per k-step (the loop's MFMAs / mfmas_per_k_step, default 8), what the loop around it holds
-outside the k loop (the per-unit bookkeeping, counted statically), and the kernel's registers and scratch.  --source compiles another copy of the file (the parent's, say) with csrc/ as the include directory.
+outside the k loop (the per-unit bookkeeping, counted statically), per unit loop what lies between its s_barrier and the first MFMA
+behind it (scalar, vector, vector-memory, and the compares / selects / lane moves / multiplies among them), and the kernel's registers and scratch.  --source compiles another copy of the file (the parent's, say) with csrc/ as the include directory.
 
 Third form, conv_wino4_kernel (its stage loop spans several basic blocks):
     isa_census.py --wino4 [--source FILE]
@@ -39,7 +40,7 @@ def loops_census(argv):
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-S", "--cuda-device-only",
                                "-I", csrc, source or os.path.join(csrc, src), "-o", out], stderr=subprocess.DEVNULL)
         text = open(out).read()
-    m = re.search(r"^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\s*s_endpgm" % re.escape(kern), text, re.S | re.M)
+    m = re.search(r"^(_Z\w*%s\w*):[^\n]*\n(.*?)\n\.Lfunc_end" % re.escape(kern), text, re.S | re.M)     # (the whole function: it may end in several places)
     name, body = m.group(1), m.group(2)
 
     def meta(key):
@@ -83,6 +84,57 @@ def loops_census(argv):
             c[x] = c.get(x, 0) + 1
         return dict(sorted(c.items()))
 
+    def barrier_to_first_mfma(header):
+        """What a wave runs between the s_barrier at the top of the unit loop `header` and the first MFMA behind it: the blocks
+        reachable from the barrier (branch targets and fall-through), each up to its first MFMA, every instruction counted once
+        (static: both sides of every branch, so also the k-step's own operand reads and transform on the path it lies on)."""
+        blocks, order, cur = {}, [], None
+        for ln in body.splitlines():
+            lab = re.match(r"^\.L(BB\d+_\d+):(.*)", ln) or re.match(r"^; (%bb\.\d+):(.*)", ln)
+            if lab:
+                cur = lab.group(1)
+                order.append(cur)
+                if cur == header or re.search(r"(Header=|Parent Loop )%s " % header, lab.group(2)):
+                    blocks[cur] = []             # a block of this unit loop; the walk does not leave it
+            elif cur in blocks and ln.startswith("\t") and not ln.strip().startswith((";", ".")):
+                tok = ln.split(";")[0].split()
+                blocks[cur].append((tok[0], tok[-1][2:] if tok[0].startswith(("s_cbranch", "s_branch")) else None))
+        start = next((b for b in order if any(i == "s_barrier" for i, _ in blocks.get(b, []))), None)
+        if start is None:
+            return None
+        seen, todo, got = set(), [(start, True)], []
+        while todo:
+            b, first = todo.pop()
+            if b in seen and not first:
+                continue
+            seen.add(b)
+            if b not in blocks:              # the loop's exit
+                continue
+            ins = blocks[b]
+            if first:
+                ins = ins[[i for i, _ in ins].index("s_barrier") + 1:]
+            done = False
+            for i, tgt in ins:
+                if i.startswith("v_mfma"):
+                    done = True
+                    break
+                got.append(i)
+                if tgt and tgt not in seen:
+                    todo.append((tgt, False))
+                if i == "s_branch":
+                    done = True
+                    break
+            if not done:
+                nxt = order.index(b) + 1
+                if nxt < len(order) and order[nxt] not in seen:
+                    todo.append((order[nxt], False))
+        valu = [x for x in got if x.startswith("v_")]
+        bad = [x for x in got if x.startswith(("v_cmp", "v_cndmask", "v_readlane", "v_writelane", "v_readfirstlane", "s_mul_hi", "s_mul_i32"))]
+        return {"scalar": sum(x.startswith("s_") and not x.startswith(("s_waitcnt", "s_nop")) for x in got), "vector": len(valu),
+                "vector_memory": sum(x.startswith(("buffer_", "global_")) for x in got), "lds": sum(x.startswith("ds_") for x in got),
+                "s_nop": sum(x == "s_nop" for x in got), "branches": sum(x.startswith(("s_cbranch", "s_branch")) for x in got),
+                "vector_by_mnemonic": by_mnemonic(valu), "compares_selects_lane_moves_multiplies": by_mnemonic(bad)}
+
     rows = []
     for label, block in loops:
         mfma = sum(x.startswith("v_mfma") for x in block)
@@ -98,8 +150,14 @@ def loops_census(argv):
         rows[-1]["per_unit_outside_the_k_loop (static: both sides of every branch)"] = {
             "vector": sum(x.startswith("v_") for x in unit), "scalar": sum(x.startswith("s_") and not x.startswith(("s_waitcnt", "s_nop")) for x in unit),
             "vector_memory": sum(x.startswith(("buffer_", "global_")) for x in unit)}
+    # per wave variant (= per depth-1 loop with a barrier, in the order of the listing): the unit boundary
+    units = []
+    for hdr in re.findall(r"^\.L(BB\d+_\d+):[^\n]*This Loop Header: Depth=1", body, re.M):
+        c = barrier_to_first_mfma(hdr)
+        if c:
+            units.append({"unit_loop": hdr, "between_the_barrier_and_the_first_mfma": c})
     print(json.dumps({"kernel": name, "source": source or src, "vgprs": meta("num_vgpr"), "agprs": meta("num_agpr"),
-                      "scratch_bytes": meta("private_seg_size"), "mfma_loops": rows}, indent=1))
+                      "scratch_bytes": meta("private_seg_size"), "mfma_loops": rows, "unit_loops": units}, indent=1))
 
 
 def wino4_census(argv):
