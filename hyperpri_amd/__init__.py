@@ -15,12 +15,13 @@ from .distance import (boundary_reference, centerline_counts, centerline_from_co
                        surface_hist_reference, surface_metrics_from_hist, thin_reference)
 from .evaluate import (CLEAN_LOGIT, SplitPrediction, centerline_metrics, clean_prediction, cluster_split, color_classmaps, color_segmaps,  # noqa: F401
                        default_class_palette, detect_split, evaluate_multiclass, object_metrics, predict_split, surface_metrics, test_net, tta_merge,
-                       refine_split, unmix_split, validate_net, write_segmaps, write_spreadmaps)
+                       enhance_split, refine_split, ridge_split, unmix_split, validate_net, write_segmaps, write_spreadmaps)
 from .evaluate import root_traits as split_root_traits  # noqa: F401  (``root_traits`` is the per-tensor call of distance.py)
 from .guided import GuidedFilter, guided_bound, guided_bruteforce, guided_filter, guided_reference  # noqa: F401
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)
+from .ridge import RidgeFilter, ridge_bound, ridge_bruteforce, ridge_filter, ridge_reference, ridge_taps  # noqa: F401
 from .spectral import (SpectralProjection, SpectralStats, band_statistics, class_spectra, gram_reference, merge_statistics,  # noqa: F401
                        moments_reference, pca_basis, project_reference)
 from .tta import TTA, VIEW_NAMES, apply_view, invert_view, tta_merge_reference  # noqa: F401

@@ -348,6 +348,72 @@ def refine_split(pred: SplitPrediction, batches: Iterable[dict], guide, radius: 
     return SplitPrediction(torch.cat(logits), pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
 
 
+def ridge_split(batches: Iterable[dict], plane, sigmas, **ridge) -> SplitPrediction:
+    """``detect_split`` for the classical spatial baseline (``hyperpri_amd.ridge_filter``, ``csrc/ridge.hip``): per batch
+    ``plane(batch["image"])`` -- a ``SpectralProjection``, or any callable that returns ``(N, 1 or T, h, w)`` (or ``(N, 1, T, h, w)``),
+    ``lambda im: proj(im)[:, :1]`` for instance -- is ridge-filtered at ``sigmas`` (``**ridge``: ``measure``, ``polarity``, ``beta``, ``c``,
+    ``domain``) and ``output="logit"`` of map 0 is stored as ``logits``, with masks, offsets, sizes and names exactly as
+    ``predict_split`` stores them, so the evaluation functions read it unchanged."""
+    from .ridge import ridge_filter
+    if "output" in ridge or "return_scale" in ridge or "return_hessian" in ridge:
+        raise ValueError("ridge_split: it stores output='logit' of the response; output, return_scale and return_hessian are not its to take")
+    logits: List[torch.Tensor] = []
+    masks: List[torch.Tensor] = []
+    offsets, sizes, names = [0], [], []
+    with torch.inference_mode():
+        for batch in batches:
+            image, mask = batch["image"], batch["mask"]
+            _require_cuda(image, "evaluation image")
+            _require_device(mask, "evaluation mask")
+            maps = plane(image)
+            if maps.dim() == 5 and maps.shape[1] == 1:
+                maps = maps[:, 0]
+            if maps.dim() != 4:
+                raise ValueError(f"ridge_split: the plane must be (N, T, h, w) or (N, 1, T, h, w), got {tuple(maps.shape)}")
+            pred = ridge_filter(maps[:, :1], sigmas, output="logit", **ridge)[:, 0]
+            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
+            if mask.numel() != n * h * w:
+                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
+                                 f"and a mask {tuple(mask.shape)}")
+            logits.append(pred.reshape(-1))
+            masks.append(mask.to(torch.float32).reshape(-1).clone())
+            names.extend(_names(batch.get("index"), n))
+            for _ in range(n):
+                offsets.append(offsets[-1] + h * w)
+                sizes.append((h, w))
+        if not logits:
+            raise ValueError("ridge_split: no batches")
+        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+
+
+def enhance_split(pred: SplitPrediction, sigmas, **ridge) -> SplitPrediction:
+    """The ridge measure of a stored split's probabilities (``hyperpri_amd.ridge_filter`` with ``domain="prob"`` and
+    ``output="logit"``; ``**ridge``: ``measure``, ``polarity``, ``beta``, ``c``): lines are kept, blobs and flat background suppressed.  It
+    reads no cube, so it needs no batches.  Returns a new ``SplitPrediction`` with the same masks, offsets, sizes and names; ``spread``
+    is carried over, as in ``refine_split``."""
+    from .ridge import ridge_filter
+    if "output" in ridge or "domain" in ridge or "return_scale" in ridge or "return_hessian" in ridge:
+        raise ValueError("enhance_split: it reads probabilities and stores logits; domain, output, return_scale and return_hessian are "
+                         "not its to take")
+    if len(pred) == 0:
+        raise ValueError("enhance_split: an empty split")
+    _require_cuda(pred.logits, "stored logits")
+    logits: List[torch.Tensor] = []
+    with torch.inference_mode():
+        i = 0
+        while i < len(pred):                                      # runs of images of one size go through one launch
+            j = i + 1
+            while j < len(pred) and pred.sizes[j] == pred.sizes[i]:
+                j += 1
+            h, w = pred.sizes[i]
+            a, b = pred.offsets[i], pred.offsets[j]
+            if b - a != (j - i) * h * w:
+                raise ValueError(f"enhance_split: images {i}..{j - 1} hold {b - a} values, their sizes say {(j - i) * h * w}")
+            logits.append(ridge_filter(pred.logits[a:b].view(j - i, h, w), sigmas, domain="prob", output="logit", **ridge).reshape(-1))
+            i = j
+    return SplitPrediction(torch.cat(logits), pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
+
+
 def _bce(logits: torch.Tensor, masks: torch.Tensor) -> float:
     n = logits.numel()
     nws = _lib.load().hpri_bce_workspace_doubles(n)

@@ -1027,6 +1027,53 @@ int hpri_guided_coeffs(const float* guide, int gs, int K, const float* maps, int
 int hpri_guided_apply(const float* guide, int gs, int K, int N, int T, int H, int W, int radius, int domain, const void* workspace,
                       size_t workspace_bytes, float* out, hipStream_t stream);
 
+/* ---- ridge filter: multi-scale Hessian vesselness for thin roots (ridge.hip; hyperpri_amd/ridge.py) -----------------------------
+ * A scale-normalised Hessian ridge measure (after Frangi et al. and Sato et al.) of T >= 1 fp32 planes on an (N, H, W) frame.  Pixel
+ * (y, x) of plane t of image n is maps[n image_stride + t plane_stride + (y W + x) pixel_stride] (strides in floats, pixel_stride >= 1):
+ * a contiguous (N, T, H, W) tensor has (T H W, H W, 1), the first T channels of a channels-last buffer of cs channels (H W cs, 1, cs);
+ * nothing else of the buffer is read.  domain 0 (linear) reads the values as they are, domain 1 (prob) sigmoid(z) of stored logits z,
+ * as hpri_guided_coeffs does.
+ *   scales  1 <= S <= hpri_ridge_max_scales (8).  Per scale s the host passes radii[s] = R in [1, hpri_ridge_max_radius (12)], the
+ *       fp32 value sigma2[s] and three half-kernels taps[(3 s + k) 12 + j - 1], k = 0, 1, 2 for g0, g1, g2 and j = 1 .. R (host
+ *       memory, S x 3 x 12 floats, entries past R ignored).  hyperpri_amd.ridge.ridge_taps makes them in fp64 and rounds them once:
+ *       w(x) = exp(-x^2 / 2 sigma^2), g0 = w / (1 + 2 sum w), g1 = x w / (2 sum x^2 w), g2 = q / sum x^2 q with q = (x^2 / sigma^4 -
+ *       1 / sigma^2) w, R = ceil(3 sigma).  There is no centre tap: every pass works on differences from its own centre, the implied
+ *       centre taps are 1 - 2 sum g0, 0 and -2 sum g2, so the kernels are exactly unit-sum (g0) or zero-sum (g1, g2) whatever the
+ *       rounding of the taps.
+ *   borders  half-sample symmetric reflection rho (d c b a | a b c d), of period 2n: defined on images smaller than R, down to 1 x 1.
+ *   row pass  per pixel and scale, fp32 from +0.0, c = I[y, x], for j = 1 .. R:
+ *       dp = I[y, rho(x+j)] - c,  dm = I[y, rho(x-j)] - c
+ *       s0 = fmaf(g0[j], dp + dm, s0),  r1 = fmaf(g1[j], dp - dm, r1),  r2 = fmaf(g2[j], dp + dm, r2)
+ *       (s0 is the smoothed plane minus the pixel; the pixel is never added back into an fp32 value)
+ *   column pass  fp32 from +0.0, for i = 1 .. R, + and - the rows rho(y + i) and rho(y - i) at the same x, c the pixel's own row:
+ *       axx = fmaf(g0[i], (r2+ - r2c) + (r2- - r2c), axx),   Hxx = (r2c + axx) sigma2
+ *       axy = fmaf(g1[i], r1+ - r1-, axy),                   Hxy = axy sigma2
+ *       ayy = fmaf(g2[i], e+ + e-, ayy),                     Hyy = ayy sigma2,    e+- = (I+- - Ic) + (s0+- - s0c)
+ *       (Lindeberg's normalisation, gamma = 1: one product by sigma2 each)
+ *   measure  per pixel and scale in fp64 from the three fp32 values, no contraction:  mu = (Hxx + Hyy) / 2,
+ *       d = sqrt(((Hxx - Hyy) / 2)^2 + Hxy^2).  polarity 0 (bright): l2 = mu - d, l1 = mu + d, gate mu < 0; 1 (dark): l2 = mu + d,
+ *       l1 = mu - d, gate mu > 0; 2 (both): mu >= 0 gives l2 = mu + d, l1 = mu - d, else l2 = mu - d, l1 = mu + d, no gate.
+ *       measure 0 (frangi): V = exp(-(l1 / l2)^2 / (2 beta^2)) (-expm1(-(l1^2 + l2^2) / (2 c^2))) where the gate holds and l2 != 0,
+ *       else 0.  measure 1 (sato): V = max(-l2, 0), max(l2, 0), |l2| for bright, dark, both.
+ *   across scales  the maximum of V over the scales in the order given; scale (may be NULL) receives the index of the first scale
+ *       that attains it.  output 0 (value): out = (float) V.  output 1 (logit): out = logf(p) - log1pf(-p) of p = clamp((float) P,
+ *       2^-24, 1 - 2^-24), P = V (frangi) or V / (V + c) (sato): the clamp and the logit of hpri_band_detect and hpri_band_unmix.
+ *       hessian (may be NULL): fp32 (N, T, S, 3, H, W), Hxx | Hxy | Hyy.
+ * One launch: a workgroup owns a tile of hpri_ridge_tile_h x hpri_ridge_tile_w pixels, one lane a pixel, with the reflected halo of
+ * the largest R in LDS.  No atomics: the result of a pixel depends on its neighbourhood and its distance to the image borders, not on
+ * N, T, the other maps, the grid, the tile or its place in a tile; a scale's Hessian planes do not depend on the other scales;
+ * identical arguments give identical bits.  A constant plane of any magnitude gives H = +0.0 and V = 0; negating the input negates H.
+ * Argument errors (a null maps, taps, radii, sigma2 or out, a size < 1, N T H W >= 2^31, S outside [1, 8], a radius outside [1, 12],
+ * a pixel stride < 1 or a negative stride, a non-finite tap, sigma2, beta or c, beta <= 0 or c <= 0, a code out of range, a misaligned
+ * pointer) return -1 before any launch. */
+int hpri_ridge_max_scales(void);
+int hpri_ridge_max_radius(void);
+int hpri_ridge_tile_h(void);
+int hpri_ridge_tile_w(void);
+int hpri_ridge_filter(const float* maps, long long image_stride, long long plane_stride, long long pixel_stride, int N, int T, int H,
+                      int W, const float* taps, const int* radii, const float* sigma2, int S, float beta, float c, int polarity,
+                      int measure, int domain, int output, float* out, unsigned char* scale, float* hessian, hipStream_t stream);
+
 /* ---- soft skeletons and the centerline loss clDice (skeleton.hip; hyperpri_amd/trainer.py, distance.py) ------------------------
  * fp32 planes (N, h, w), contiguous, values meant to lie in [0, 1]; 0 <= iters <= hpri_soft_skeleton_max_iters (32).
  *   E(I)[u] = min over the in-image part of the plus neighbourhood {N, W, C, E, S} of u,  D(I)[u] = max over the in-image 3x3
