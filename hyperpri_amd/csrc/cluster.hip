@@ -8,11 +8,11 @@
 // For a centroid g the caller passes W[k] = -g and b[k] = |g|^2 / 2: z is half the squared distance minus |d|^2 / 2, and
 // max(0, 2 zmin + s) is the squared distance to the nearest centroid.  The kernels know nothing of that.
 //
-// Scores.  The tile pipeline of band_project_kernel: W transposed in LDS for the workgroup's lifetime (wl[c][kp], column n of row c at
-// n ^ 16 (c & 1)), a tile of CL_TILE = 64 pixels as d at a row stride of band_tile_stride(cs), each wave 16 pixels against every block of
-// 16 rows on v_mfma_f32_16x16x4_f32 (i = row k, j = pixel, k = band).  Where W at ks = 64 and 64 pixels do not fit the LDS together
-// (cs > 304) the tile is 32 pixels and two waves score.  s is the diagonal of the same product with the pixel on both sides
-// (A == B == the register that holds d): D[i][i] of the 16 x 16 tile is the chain above, bit for bit.
+// Scores.  The batch-tile pipeline of band_common.h: W transposed in LDS for the workgroup's lifetime (band_stage_rows), a tile of
+// CL_TILE = 64 pixels as d at a row stride of band_tile_stride(cs), each wave 16 pixels against every block of 16 rows (band_scores).
+// Where W at ks = 64 and 64 pixels do not fit the LDS together (cs > 304) the tile is 32 pixels and two waves score.  s is the diagonal
+// of the same product with the pixel on both sides (A == B == the register that holds d): D[i][i] of the 16 x 16 tile is the chain
+// above, bit for bit.
 // Argmin.  A lane holds the rows 16 kb + 4 (l >> 4) + j, j < 4, of its pixel; it scans them in ascending k (a later row wins only when
 // it is strictly smaller), then the four lanes of a pixel exchange (z, k) over xor 16 and xor 32 and keep the smaller z, the lower k
 // between equal z.  Rows >= K never enter.  A lane without a row starts at k = -1 and takes whatever comes: label < K for every
@@ -35,65 +35,13 @@
 #define CL_PARTS 256
 #define CL_LOADS ((CL_TILE * (BAND_MAX_CS / 4) + BAND_THREADS - 1) / BAND_THREADS)
 
-static inline __host__ __device__ int cl_kp(int nkb) { return (nkb * 16 + 31) & ~31; }
-
 // LDS of either kernel, in words: wl [cs][kp], xl [tile][ldx], the pivot [cs], the labels [CL_TILE], then 64 counters and 2 x 64
 // doubles of 8 bytes
 static inline size_t cl_lds_bytes(int cs, int ks, int tile) {
-  const int kp = cl_kp((ks + 15) / 16);
+  const int kp = band_kp((ks + 15) / 16);
   return ((size_t)cs * kp + (size_t)tile * band_tile_stride(cs) + cs + CL_TILE) * 4 + (size_t)CL_MAX_K * 8 + 2 * (size_t)CL_TILE * 8;
 }
 static inline int cl_tile(int cs, int ks) { return cl_lds_bytes(cs, ks, CL_TILE) <= BAND_LDS_BYTES ? CL_TILE : CL_TILE / 2; }
-
-template <int NKB> struct ClRows { f32x4 b4[NKB]; int woff[NKB]; };
-
-// W -> LDS (transposed, swizzled) and this lane's bias quads and column offsets: band_project_kernel's prologue
-template <int NKB>
-__device__ __forceinline__ void cl_stage_rows(float* __restrict__ wl, const float* __restrict__ W, const float* __restrict__ bias, int cs,
-                                              int ks, int t, int col, int kq, ClRows<NKB>& rows) {
-  const int kp = cl_kp(NKB);
-  for (int i = t; i < cs * kp; i += BAND_THREADS) {
-    const int c = i / kp, n = i - c * kp;
-    wl[c * kp + (n ^ ((c & 1) << 4))] = n < ks ? W[(long long)n * cs + c] : 0.f;
-  }
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) {
-    const int n0 = kb * 16 + kq * 4;
-    rows.woff[kb] = (kb * 16 + col) ^ ((kq & 1) << 4);
-    rows.b4[kb] = n0 < ks ? *reinterpret_cast<const f32x4*>(bias + n0) : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-}
-
-// z of this lane's pixel (xr = its row in LDS + kq) against every block of 16 rows, and (DIAG) the 16 x 16 products of the wave's pixels
-// with themselves, whose diagonal is s.  cs % 8 == 0: two k-steps per iteration, the next iteration's operands read before this one's
-// MFMAs issue (the last iteration reads its own again).
-template <int NKB, bool DIAG>
-__device__ __forceinline__ void cl_scores(const float* __restrict__ xr, const float* __restrict__ wr, const ClRows<NKB>& rows, int cs,
-                                          f32x4 (&acc)[NKB], f32x4& accd) {
-  const int kp = cl_kp(NKB);
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) acc[kb] = rows.b4[kb];
-  accd = f32x4{0.f, 0.f, 0.f, 0.f};
-  float x0 = xr[0], x1 = xr[4], w0[NKB], w1[NKB];
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) { w0[kb] = wr[rows.woff[kb]]; w1[kb] = wr[4 * kp + rows.woff[kb]]; }
-  for (int c = 0; c < cs; c += 8) {
-    const int cn = min(c + 8, cs - 8);
-    const float nx0 = xr[cn], nx1 = xr[cn + 4];
-    float nw0[NKB], nw1[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) { nw0[kb] = wr[cn * kp + rows.woff[kb]]; nw1[kb] = wr[(cn + 4) * kp + rows.woff[kb]]; }
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[kb], x0, acc[kb], 0, 0, 0);
-    if (DIAG) accd = __builtin_amdgcn_mfma_f32_16x16x4f32(x0, x0, accd, 0, 0, 0);
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[kb], x1, acc[kb], 0, 0, 0);
-    if (DIAG) accd = __builtin_amdgcn_mfma_f32_16x16x4f32(x1, x1, accd, 0, 0, 0);
-    x0 = nx0; x1 = nx1;
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) { w0[kb] = nw0[kb]; w1[kb] = nw1[kb]; }
-  }
-}
 
 // the label and its score, in every lane of the pixel (see the head of the file)
 template <int NKB>
@@ -140,15 +88,14 @@ __global__ __launch_bounds__(BAND_THREADS) void band_assign_kernel(const float* 
   extern __shared__ float cl[];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int cs = 4 * q, kp = cl_kp(NKB), ldx = band_tile_stride(cs);
+  const int cs = 4 * q, kp = band_kp(NKB), ldx = band_tile_stride(cs);
   float* wl = cl;                                      // [cs][kp]
   float* xl = wl + cs * kp;                            // [tile][ldx]
   float* pvl = xl + tile * ldx;                        // [cs]
   const int col = lane & 15, kq = lane >> 4;
-  ClRows<NKB> rows;
-  cl_stage_rows<NKB>(wl, W, bias, cs, ks, t, col, kq, rows);
+  BandRows<NKB> rows;
+  band_stage_rows<NKB>(wl, W, bias, cs, ks, t, col, kq, rows);
   for (int i = t; i < cs; i += BAND_THREADS) pvl[i] = pivot != nullptr ? pivot[i] : 0.f;
-  const int total = tile * q;
   const long long tiles = (P + tile - 1) / tile;
   f32x4 v[CL_LOADS];
   // (q is hidden from the optimiser per tile, as band_gram_kernel hides it: the quotients idx / q and the addresses made of them would
@@ -157,6 +104,8 @@ __global__ __launch_bounds__(BAND_THREADS) void band_assign_kernel(const float* 
   auto load = [&](long long tl) {
     const long long p0 = tl * tile;
     const int left = (int)min((long long)tile, P - p0) * ql;       // quads of the tile that lie inside the batch
+    // (band_tile_load with its 64-bit addresses: on 32-bit offsets from the tile's first quad the label map at K = 2 and 8 measured
+    // 2 % slower, profiles/band_pipeline_refactor.json)
 #pragma unroll
     for (int u = 0; u < CL_LOADS; ++u) {
       const int idx = t + u * BAND_THREADS;
@@ -164,26 +113,17 @@ __global__ __launch_bounds__(BAND_THREADS) void band_assign_kernel(const float* 
       if (idx < left) v[u] = *reinterpret_cast<const f32x4*>(x + p0 * cs + 4LL * idx);
     }
   };
+  const auto centre = [pvl](f32x4 w, int cq) { return w - *reinterpret_cast<const f32x4*>(pvl + 4 * cq); };
   if (blockIdx.x < tiles) load(blockIdx.x);
   for (long long tl = blockIdx.x; tl < tiles; tl += gridDim.x) {
     __syncthreads();                                   // (the rows and the pivot are in LDS; the previous tile has been consumed)
     asm volatile("" : "+s"(ql));
-#pragma unroll
-    for (int u = 0; u < CL_LOADS; ++u) {
-      const int idx = t + u * BAND_THREADS;
-      if (idx < total) {
-        const int px = idx / ql, cq = idx - px * ql;
-        const f32x4 d = v[u] - *reinterpret_cast<const f32x4*>(pvl + 4 * cq);
-        float2* dst = reinterpret_cast<float2*>(xl + px * ldx + 4 * cq);
-        dst[0] = float2{d[0], d[1]};
-        dst[1] = float2{d[2], d[3]};
-      }
-    }
+    band_tile_stage<CL_LOADS, BAND_THREADS>(xl, v, t, tile * q, ql, ldx, centre);
     __syncthreads();
     if (tl + gridDim.x < tiles) load(tl + gridDim.x);
     if (wave * 16 < tile) {
       f32x4 acc[NKB], accd;
-      cl_scores<NKB, DIAG>(xl + (wave * 16 + col) * ldx + kq, wl + kq * kp, rows, cs, acc, accd);
+      band_scores<NKB, DIAG>(xl + (wave * 16 + col) * ldx + kq, wl + kq * kp, rows, cs, acc, accd);
       int label;
       float zmin;
       cl_argmin<NKB>(acc, K, kq, label, zmin);
@@ -213,7 +153,7 @@ __global__ __launch_bounds__(BAND_THREADS) void band_cluster_kernel(const T* __r
   extern __shared__ float cl[];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int cs = 4 * q, kp = cl_kp(NKB), ldx = band_tile_stride(cs), nb = (cs + 31) >> 5;
+  const int cs = 4 * q, kp = band_kp(NKB), ldx = band_tile_stride(cs), nb = (cs + 31) >> 5;
   const int ntiles = ((K + 31) >> 5) * nb;
   float* wl = cl;                                      // [cs][kp]
   float* xl = wl + cs * kp;                            // [tile][ldx]
@@ -222,8 +162,8 @@ __global__ __launch_bounds__(BAND_THREADS) void band_cluster_kernel(const T* __r
   unsigned long long* cnt = reinterpret_cast<unsigned long long*>(lab + CL_TILE);       // [CL_MAX_K]
   double* tot = reinterpret_cast<double*>(cnt + CL_MAX_K);                              // [2][CL_TILE]
   const int col = lane & 15, kq = lane >> 4;
-  ClRows<NKB> rows;
-  cl_stage_rows<NKB>(wl, W, bias, cs, ks, t, col, kq, rows);
+  BandRows<NKB> rows;
+  band_stage_rows<NKB>(wl, W, bias, cs, ks, t, col, kq, rows);
   for (int i = t; i < cs; i += BAND_THREADS) pvl[i] = pivot != nullptr ? pivot[i] : 0.f;
   for (int i = t; i < tile * ldx; i += BAND_THREADS) xl[i] = 0.f;          // (the columns [cs, ldx) stay zero)
   if (t < CL_MAX_K) cnt[t] = 0ull;
@@ -298,7 +238,7 @@ __global__ __launch_bounds__(BAND_THREADS) void band_cluster_kernel(const T* __r
       if (c0 + tile < run.len) load(c0 + tile, pxs, cqs);
       if (wave * 16 < tile) {
         f32x4 sc[NKB], accd;
-        cl_scores<NKB, true>(xl + (wave * 16 + col) * ldx + kq, wl + kq * kp, rows, cs, sc, accd);
+        band_scores<NKB, true>(xl + (wave * 16 + col) * ldx + kq, wl + kq * kp, rows, cs, sc, accd);
         int label;
         float zmin;
         cl_argmin<NKB>(sc, K, kq, label, zmin);
@@ -401,24 +341,16 @@ static inline size_t cl_part_doubles(int cs, int K) { return (size_t)((K + 31) /
 
 // 0 for a channel stride or a K the pass does not take
 extern "C" size_t hpri_band_cluster_workspace_bytes(int cs, int K) {
-  if (cs <= 0 || cs % 8 != 0 || cs > BAND_MAX_CS || K <= 0 || K > CL_MAX_K) return 0;
+  if (!band_cs_ok(cs) || K <= 0 || K > CL_MAX_K) return 0;
   return (size_t)CL_PARTS * (cl_part_doubles(cs, K) + CL_MAX_K + 2) * 8;
 }
-
-// (more than 64 KB of dynamic LDS has to be asked for, per device; a runtime that needs no such request may refuse it: the launch
-// reports what matters)
-#define CL_ASK_LDS(kernel_, lds_)                                                                                                  \
-  do {                                                                                                                             \
-    if ((lds_) > 64 * 1024 && hipFuncSetAttribute((const void*)kernel_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_)) != hipSuccess) \
-      (void)hipGetLastError();                                                                                                     \
-  } while (0)
 
 extern "C" int hpri_band_assign(const float* x, long long pixels, int cs, const float* pivot, const float* centers, const float* bias,
                                 int K, const float* lut, unsigned char* labels, float* zmin, float* dist2, float* value,
                                 hipStream_t stream) {
   HPRI_REQUIRE(x && centers && bias, "band_assign: null pointer");
   HPRI_REQUIRE(pixels > 0, "band_assign: bad sizes");
-  HPRI_REQUIRE(cs > 0 && cs % 8 == 0 && cs <= BAND_MAX_CS, "band_assign: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
+  HPRI_REQUIRE(band_cs_ok(cs), "band_assign: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
   HPRI_REQUIRE(K > 0 && K <= CL_MAX_K, "band_assign: K must lie in [1, hpri_band_cluster_max_k]");
   HPRI_REQUIRE(labels || zmin || dist2 || value, "band_assign: nothing to write");
   HPRI_REQUIRE((value != nullptr) == (lut != nullptr), "band_assign: value and lut come together");
@@ -431,7 +363,7 @@ extern "C" int hpri_band_assign(const float* x, long long pixels, int cs, const 
   const dim3 grid = cache_grid(tiles, (int)(per_cu < 1 ? 1 : per_cu > 4 ? 4 : per_cu));
 #define CL_ASSIGN_LAUNCH(NKB_, DIAG_)                                                                                              \
   do {                                                                                                                             \
-    CL_ASK_LDS((band_assign_kernel<NKB_, DIAG_>), lds);                                                                            \
+    hpri_ask_dynamic_lds(band_assign_kernel<NKB_, DIAG_>, lds);                                                                    \
     hipLaunchKernelGGL((band_assign_kernel<NKB_, DIAG_>), grid, dim3(BAND_THREADS), lds, stream, x, pixels, cs / 4, pivot, centers, bias, \
                        ks, K, tile, lut, labels, zmin, dist2, value);                                                              \
   } while (0)
@@ -475,11 +407,11 @@ extern "C" int hpri_band_cluster_sums(const void* cache, int cache_dtype, int sl
 #define CL_SUMS_LAUNCH(NKB_)                                                                                                       \
   do {                                                                                                                             \
     if (cache_dtype == 0) {                                                                                                        \
-      CL_ASK_LDS((band_cluster_kernel<float, NKB_>), lds);                                                                         \
+      hpri_ask_dynamic_lds(band_cluster_kernel<float, NKB_>, lds);                                                                 \
       hipLaunchKernelGGL((band_cluster_kernel<float, NKB_>), dim3(parts), dim3(BAND_THREADS), lds, stream, (const float*)cache, masks, \
                          slot_table, slots, P, cs / 4, rps, runs, select, pivot, centers, bias, ks, K, tile, part, part_cnt, part_tot); \
     } else {                                                                                                                       \
-      CL_ASK_LDS((band_cluster_kernel<_Float16, NKB_>), lds);                                                                      \
+      hpri_ask_dynamic_lds(band_cluster_kernel<_Float16, NKB_>, lds);                                                              \
       hipLaunchKernelGGL((band_cluster_kernel<_Float16, NKB_>), dim3(parts), dim3(BAND_THREADS), lds, stream, (const _Float16*)cache, \
                          masks, slot_table, slots, P, cs / 4, rps, runs, select, pivot, centers, bias, ks, K, tile, part, part_cnt,  \
                          part_tot);                                                                                                \

@@ -9,8 +9,8 @@
 // cosine t * rsqrt(q), or the logit of either).  Nothing of size P x K ever leaves the workgroup.
 //
 // Layout.  A workgroup is eight waves and owns one tile of DET_TILE = 64 pixels at a time (a persistent grid of two workgroups per
-// CU -- one where two tiles do not fit the LDS -- strides over the tiles; 128 registers a lane, so that two fit).  The tile sits in LDS as band_project_kernel keeps it -- rows at a stride of ldx = cs + 2 rounded to
-// 2 (mod 32) words, so the 32 lanes of a ds_read_b32 group (2 i + k) hit 32 banks, written as 8-byte pairs -- and is the B operand of
+// CU -- one where two tiles do not fit the LDS -- strides over the tiles; 128 registers a lane, so that two fit).  The tile sits in LDS as band_common.h keeps it
+// (band_tile_load, band_tile_stage: rows at band_tile_stride(cs), written as 8-byte pairs) and is the B operand of
 // EVERY wave: it is read from HBM once, with 16-byte loads, and the next tile travels global -> registers while this one is
 // multiplied.  W at cs = 240 is 245 KB and fits no LDS beside a tile, so the 16-row blocks of W are looped over and W is streamed
 // from L2: wave w owns the row blocks of its rounds (round r: block 8 r + w, or 8 r + 7 - w in odd rounds -- the serpentine pairs a
@@ -30,17 +30,13 @@
 // Identity metric (W == NULL, Kq == 0): q = fmaf(x[c], x[c], q) and t[j] = fmaf(F[j][c], x[c], t[j]) ascending c from 0 (from b[j]
 // with a bias), F the (T, cs) filter rows.  No matrix unit: the same tile pipeline (one sweep, 16-byte loads), one thread per
 // (pixel, chain).
-#include "cache_launch.h"
+#include "band_common.h"
 
 #define DET_THREADS 512
 #define DET_WAVES 8
 #define DET_TILE 64
 #define DET_MAX_T 8
-#define DET_MAX_CS 320                  // hpri_band_max_cs (spectral.hip: BAND_MAX_CS)
-#define DET_LOADS ((DET_TILE * (DET_MAX_CS / 4) + DET_THREADS - 1) / DET_THREADS)
-#define DET_LDS_BYTES (160 * 1024)
-#define DET_P_LO 5.9604644775390625e-08f    // 2^-24
-#define DET_P_HI 0.99999994039535522f       // 1 - 2^-24
+#define DET_LOADS ((DET_TILE * (BAND_MAX_CS / 4) + DET_THREADS - 1) / DET_THREADS)
 
 // cend[rb] / 8, one byte per block: a table in registers (an array argument indexed by a loop variable would live in scratch)
 struct DetExtents { unsigned long long w[3]; };
@@ -48,11 +44,6 @@ struct DetExtents { unsigned long long w[3]; };
 __device__ __forceinline__ int det_extent(const DetExtents& e, int rb) {
   const unsigned long long v = rb < 8 ? e.w[0] : rb < 16 ? e.w[1] : e.w[2];
   return (int)((v >> (8 * (rb & 7))) & 255ull) * 8;
-}
-
-__device__ __forceinline__ float det_logit(float s) {
-  const float p = fminf(fmaxf(s, DET_P_LO), DET_P_HI);
-  return logf(p) - log1pf(-p);
 }
 
 template <bool IDENTITY>
@@ -63,43 +54,26 @@ __global__ __launch_bounds__(DET_THREADS, 4) void band_detect_kernel(const float
   extern __shared__ float dl[];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int cs = 4 * q4, ldx = cs + 2 + ((32 - (cs & 31)) & 31);
+  const int cs = 4 * q4, ldx = band_tile_stride(cs);
   float* xl = dl;                                      // [DET_TILE][ldx]
   float* qb = dl + DET_TILE * ldx;                     // [DET_WAVES * 4][DET_TILE] partial q (identity: row 0 holds q)
   float* tb = qb + DET_WAVES * 4 * DET_TILE;           // [DET_MAX_T][DET_TILE] filter outputs
   const int col = lane & 15, kq = lane >> 4;
   const int nrb = (Kq + T + 15) >> 4;
-  const int total = DET_TILE * q4;
   const long long tiles = (P + DET_TILE - 1) / DET_TILE;
   f32x4 v[DET_LOADS];
   // (q4 is hidden from the optimiser per tile, as band_gram_kernel hides it: the ten quotients idx / q4 and the addresses made of
   // them would otherwise be computed once and held in registers across the k loops)
   int ql = q4;
   auto load = [&](long long tile) {
-    const long long p0 = tile * DET_TILE;
-    const float* src = x + p0 * cs;
-    const int left = (int)min((long long)DET_TILE, P - p0) * ql;     // quads of the tile that lie inside the batch
-#pragma unroll
-    for (int u = 0; u < DET_LOADS; ++u) {
-      const int idx = t + u * DET_THREADS;
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (idx < left) v[u] = *reinterpret_cast<const f32x4*>(src + 4 * idx);
-    }
+    const long long p0 = tile * DET_TILE;              // (left: the quads of the tile that lie inside the batch)
+    band_tile_load<DET_LOADS, DET_THREADS>(v, x + p0 * cs, t, (int)min((long long)DET_TILE, P - p0) * ql);
   };
   if (blockIdx.x < tiles) load(blockIdx.x);
   for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     __syncthreads();                                   // (the previous tile and its partials have been consumed)
     asm volatile("" : "+s"(ql));
-#pragma unroll
-    for (int u = 0; u < DET_LOADS; ++u) {
-      const int idx = t + u * DET_THREADS;
-      if (idx < total) {
-        const int px = idx / ql, cq = idx - px * ql;
-        float2* d = reinterpret_cast<float2*>(xl + px * ldx + 4 * cq);
-        d[0] = float2{v[u][0], v[u][1]};
-        d[1] = float2{v[u][2], v[u][3]};
-      }
-    }
+    band_tile_stage<DET_LOADS, DET_THREADS>(xl, v, t, DET_TILE * q4, ql, ldx, BandQuadAsIs());
     __syncthreads();
     if (tile + gridDim.x < tiles) load(tile + gridDim.x);
     if (IDENTITY) {
@@ -199,10 +173,10 @@ __global__ __launch_bounds__(DET_THREADS, 4) void band_detect_kernel(const float
           if (j < T) {
             float s = tb[j * DET_TILE + px];
             if (score & 1) s = qv == 0.f ? 0.f : s * rsqrtf(qv);
-            if (score & 2) s = det_logit(s);
+            if (score & 2) s = hpri_clamped_logit(s);
             scores[(long long)j * P + pix] = s;
           } else if (qout != nullptr) {
-            qout[pix] = (!IDENTITY && (score & 2)) ? det_logit(qv / (qv + (float)Kq)) : qv;
+            qout[pix] = (!IDENTITY && (score & 2)) ? hpri_clamped_logit(qv / (qv + (float)Kq)) : qv;
           }
         }
       }
@@ -212,8 +186,7 @@ __global__ __launch_bounds__(DET_THREADS, 4) void band_detect_kernel(const float
 
 // ---- host ------------------------------------------------------------------------------------------------------------
 static inline size_t band_detect_lds(int cs) {
-  const int ldx = cs + 2 + ((32 - (cs & 31)) & 31);
-  return ((size_t)DET_TILE * ldx + (size_t)DET_WAVES * 4 * DET_TILE + (size_t)DET_MAX_T * DET_TILE) * 4;
+  return ((size_t)DET_TILE * band_tile_stride(cs) + (size_t)DET_WAVES * 4 * DET_TILE + (size_t)DET_MAX_T * DET_TILE) * 4;
 }
 
 extern "C" int hpri_band_detect_max_targets(void) { return DET_MAX_T; }
@@ -224,7 +197,7 @@ extern "C" int hpri_band_detect(const float* x, long long pixels, int cs, const 
                                 const float* filters, const int* cend, int score, float* q, float* scores, hipStream_t stream) {
   HPRI_REQUIRE(x != nullptr, "band_detect: null pointer");
   HPRI_REQUIRE(pixels > 0 && Kq >= 0, "band_detect: bad sizes");
-  HPRI_REQUIRE(cs > 0 && cs % 8 == 0 && cs <= DET_MAX_CS, "band_detect: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
+  HPRI_REQUIRE(band_cs_ok(cs), "band_detect: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
   HPRI_REQUIRE(T >= 0 && T <= DET_MAX_T, "band_detect: T exceeds hpri_band_detect_max_targets");
   HPRI_REQUIRE(score >= 0 && score <= 3, "band_detect: score must be 0 (raw), 1 (cosine), 2 or 3 (their logits)");
   HPRI_REQUIRE((T > 0) == (scores != nullptr), "band_detect: the score planes come with the filter rows");
@@ -249,14 +222,10 @@ extern "C" int hpri_band_detect(const float* x, long long pixels, int cs, const 
   }
   const size_t lds = band_detect_lds(cs);
   const long long tiles = (pixels + DET_TILE - 1) / DET_TILE;
-  const dim3 grid = cache_grid(tiles, 2 * lds <= DET_LDS_BYTES ? 2 : 1);
-  // (more than 64 KB of dynamic LDS has to be asked for, per device; a runtime that needs no such request may refuse it: the launch
-  // reports what matters)
+  const dim3 grid = cache_grid(tiles, 2 * lds <= BAND_LDS_BYTES ? 2 : 1);
 #define BAND_DETECT_LAUNCH(ID_, W_)                                                                                                \
   do {                                                                                                                             \
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)band_detect_kernel<ID_>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                               (int)lds) != hipSuccess)                                                            \
-      (void)hipGetLastError();                                                                                                     \
+    hpri_ask_dynamic_lds(band_detect_kernel<ID_>, lds);                                                                            \
     hipLaunchKernelGGL(band_detect_kernel<ID_>, grid, dim3(DET_THREADS), lds, stream, x, pixels, cs / 4, W_, bias, ks, Kq, T, ext, \
                        score, q, scores);                                                                                          \
   } while (0)

@@ -25,8 +25,6 @@
 #define GF_MAX_K 3
 #define GF_GROUP 4                           // maps of one pass through stage 1
 #define GF_PER_CU 4                          // workgroups a CU is offered; the kernels stride over the rest
-#define GF_P_LO 5.9604644775390625e-08f      // 2^-24: the clamp of detect.hip's and unmix.hip's logit
-#define GF_P_HI 0.99999994039535522f         // 1 - 2^-24
 
 struct GfArgs {
   const float* guide;      // (N, H, W, gs)
@@ -37,11 +35,6 @@ struct GfArgs {
   long long items;         // tiles x images x (groups | maps)
   int gs, vec, N, T, H, W, r, domain, tiles_x, tiles_y, groups;
 };
-
-__device__ __forceinline__ float gf_logit(float s) {
-  const float p = fminf(fmaxf(s, GF_P_LO), GF_P_HI);
-  return logf(p) - log1pf(-p);
-}
 
 // in-image pixels of the window of coordinate v on an axis of length L
 __device__ __forceinline__ int gf_extent(int v, int r, int L) { return min(v + r, L - 1) - max(v - r, 0) + 1; }
@@ -235,7 +228,7 @@ __global__ __launch_bounds__(GF_THREADS) void guided_apply_kernel(const GfArgs g
         }
       }
       const float q = acc / (float)(gf_extent(y, r, g.H) * gf_extent(x, r, g.W));
-      g.out[rest * hw + (long long)y * g.W + x] = g.domain ? gf_logit(q) : q;
+      g.out[rest * hw + (long long)y * g.W + x] = g.domain ? hpri_clamped_logit(q) : q;
     }
     __syncthreads();
   }

@@ -34,8 +34,6 @@
 #define RF_PER_CU 8                          // workgroups a CU is offered (measured at 2, 4, 6, 8); the kernel strides over the rest
 #define RF_IMG_H (RF_TILE_H + 2 * RF_MAX_R)  // 40 rows of the staged tile at the largest halo
 #define RF_IMG_W (RF_TILE_W + 2 * RF_MAX_R)  // 56 columns
-#define RF_P_LO 5.9604644775390625e-08f      // 2^-24: the clamp of detect.hip's and unmix.hip's logit
-#define RF_P_HI 0.99999994039535522f         // 1 - 2^-24
 
 struct RfArgs {
   const float* in;
@@ -50,11 +48,6 @@ struct RfArgs {
   float beta, c;
   int N, T, H, W, S, Rm, logit, tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ float rf_logit(float s) {
-  const float p = fminf(fmaxf(s, RF_P_LO), RF_P_HI);
-  return logf(p) - log1pf(-p);
-}
 
 // half-sample symmetric reflection of any integer onto [0, n)
 __device__ __forceinline__ int rf_reflect(int i, int n) {
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(RF_THREADS) void ridge_filter_kernel(const RfArgs g
       const long long o = rest * hw + (long long)y * g.W + x;
       if (g.logit) {
         const double p = MEAS == 1 ? best / (best + (double)g.c) : best;
-        g.out[o] = rf_logit((float)p);
+        g.out[o] = hpri_clamped_logit((float)p);
       } else {
         g.out[o] = (float)best;
       }

@@ -388,10 +388,7 @@ extern "C" size_t hpri_cldice_state_doubles(int N, int per_image) {
 static int sk_launch_fwd(SkFwd& a, hipStream_t stream) {
   a.tiles_x = sk_tiles(a.w, SK_T);
   const size_t lds = hpri_soft_skeleton_lds_bytes(a.iters);
-  // (more than 64 KB of dynamic LDS has to be asked for; a runtime that needs no such request may refuse it: the launch reports
-  // what matters)
-  if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)soft_skel_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    (void)hipGetLastError();
+  hpri_ask_dynamic_lds(soft_skel_fwd_kernel, lds);
   hipLaunchKernelGGL(soft_skel_fwd_kernel, dim3(a.tiles_x * sk_tiles(a.h, SK_T), a.n0 + a.n1), dim3(SK_THREADS), lds, stream, a);
   HPRI_CHECK_LAUNCH();
   return HPRI_OK;

@@ -15,7 +15,7 @@
 // BAND_GRAM_PARTS: constants, not the CU count), one workgroup per partial.  A finishing kernel adds the partials 0, 1, 2, ... in
 // fp64.  No floating-point atomic anywhere: the bits depend on the arguments and on these constants only.  The partials live in the
 // caller's workspace, whose size (hpri_band_workspace_bytes) depends on cs alone.
-#include "band_common.h"                // BAND_FP32_RUN, BAND_MAX_CS, the loads, the selection, the runs and band_check
+#include "band_common.h"                // BAND_FP32_RUN, BAND_MAX_CS, the loads, the selection, the runs, band_check; the batch-tile pipeline
 
 #define BAND_MOMENT_PARTS 2048          // partial accumulators of the moments pass (memory-bound: eight workgroups per CU)
 #define BAND_GRAM_PARTS 256             // partial accumulators of the Gram pass (MFMA-bound: one wave per SIMD)
@@ -258,88 +258,36 @@ __global__ void band_gram_finish_kernel(const double* __restrict__ part, int par
 }
 
 // ---- projection ------------------------------------------------------------------------------------------------------
-// v_mfma_f32_16x16x4_f32 with i = output channel, j = pixel, k = input channel: lane l holds A[i = l & 15][k = l >> 4] = W[i][c + k]
-// and B[k][j = l & 15] = x[pixel j][c + k]; D: column (pixel) = l & 15, row (output channel) = 4 (l >> 4) + reg, so a lane ends
-// with four consecutive output channels of one pixel: one 16-byte store.  The chain over c ascends, started from the bias: bit
-// for bit fmaf(W[k][cs-1], x[cs-1], ... fmaf(W[k][0], x[0], b[k])).
-// LDS, for the workgroup's lifetime: W transposed, wl[c][kp] (kp = 16 * blocks rounded up to 32 words; column n of row c sits at
-// n ^ 16 (c & 1), so that the two k of a 32-lane group fall into different halves of the banks).  Per tile: PROJ_TILE pixel rows
-// at a stride of ldx = cs + 2 words (ldx % 32 == 2 ... 2 i + k: the 32 lanes of a group hit 32 banks; cs % 8 == 0 makes the stride
-// even, the rows are written as 8-byte pairs).  The next tile's rows are loaded into registers (16-byte loads) before the current
-// tile is multiplied.  Each wave owns 16 pixels of the tile and every block of output channels.
+// The batch-tile pipeline of band_common.h with nothing added: W and the bias as the score rows (band_stage_rows), PROJ_TILE pixel
+// rows per tile (band_tile_load, band_tile_stage: the next tile's rows travel global -> registers before the current tile is
+// multiplied), each wave 16 pixels of the tile against every block of output channels (band_scores).  A lane ends with four
+// consecutive output channels of one pixel: one 16-byte store.
 template <int NKB>
 __global__ __launch_bounds__(BAND_THREADS) void band_project_kernel(const float* __restrict__ x, long long P, int q,
                                                                     const float* __restrict__ W, const float* __restrict__ bias,
                                                                     int ks, float* __restrict__ y) {
   extern __shared__ float pl[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int cs = 4 * q, kp = ((NKB * 16) + 31) & ~31, ldx = cs + 2 + ((32 - (cs & 31)) & 31);
+  const int cs = 4 * q, kp = band_kp(NKB), ldx = band_tile_stride(cs);
   float* wl = pl;                                      // [cs][kp]
   float* xl = pl + cs * kp;                            // [PROJ_TILE][ldx]
-  for (int i = t; i < cs * kp; i += BAND_THREADS) {
-    const int c = i / kp, n = i - c * kp;
-    wl[c * kp + (n ^ ((c & 1) << 4))] = n < ks ? W[(long long)n * cs + c] : 0.f;
-  }
   const int col = lane & 15, kq = lane >> 4;
-  f32x4 b4[NKB];
-  int woff[NKB];                                         // output channel 16 kb + col of the rows c + kq (c % 4 == 0: their parity is kq's)
-#pragma unroll
-  for (int kb = 0; kb < NKB; ++kb) {
-    const int n0 = kb * 16 + kq * 4;
-    woff[kb] = (kb * 16 + col) ^ ((kq & 1) << 4);
-    b4[kb] = n0 < ks ? *reinterpret_cast<const f32x4*>(bias + n0) : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  const int total = PROJ_TILE * q;
+  BandRows<NKB> rows;
+  band_stage_rows<NKB>(wl, W, bias, cs, ks, t, col, kq, rows);
   const long long tiles = (P + PROJ_TILE - 1) / PROJ_TILE;
   f32x4 v[PROJ_LOADS];
   auto load = [&](long long tile) {
-    const long long p0 = tile * PROJ_TILE;
-#pragma unroll
-    for (int u = 0; u < PROJ_LOADS; ++u) {
-      const int idx = t + u * BAND_THREADS;
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (idx < total && p0 + idx / q < P) v[u] = *reinterpret_cast<const f32x4*>(x + p0 * cs + 4LL * idx);
-    }
+    const long long p0 = tile * PROJ_TILE;             // (left: the quads of the tile that lie inside the batch)
+    band_tile_load<PROJ_LOADS, BAND_THREADS>(v, x + p0 * cs, t, (int)min((long long)PROJ_TILE, P - p0) * q);
   };
   if (blockIdx.x < tiles) load(blockIdx.x);
   for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < PROJ_LOADS; ++u) {
-      const int idx = t + u * BAND_THREADS;
-      if (idx < total) {
-        const int px = idx / q, cq = idx - px * q;
-        float2* d = reinterpret_cast<float2*>(xl + px * ldx + 4 * cq);
-        d[0] = float2{v[u][0], v[u][1]};
-        d[1] = float2{v[u][2], v[u][3]};
-      }
-    }
+    band_tile_stage<PROJ_LOADS, BAND_THREADS>(xl, v, t, PROJ_TILE * q, q, ldx, BandQuadAsIs());
     __syncthreads();
     if (tile + gridDim.x < tiles) load(tile + gridDim.x);
-    f32x4 acc[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) acc[kb] = b4[kb];
-    const float* xr = xl + (wave * 16 + col) * ldx + kq;
-    const float* wr = wl + kq * kp;
-    // cs % 8 == 0: two k-steps per iteration; the operands of the next iteration are read from LDS before this one's MFMAs issue
-    // (the last iteration reads its own again)
-    float x0 = xr[0], x1 = xr[4], w0[NKB], w1[NKB];
-#pragma unroll
-    for (int kb = 0; kb < NKB; ++kb) { w0[kb] = wr[woff[kb]]; w1[kb] = wr[4 * kp + woff[kb]]; }
-    for (int c = 0; c < cs; c += 8) {
-      const int cn = min(c + 8, cs - 8);
-      const float nx0 = xr[cn], nx1 = xr[cn + 4];
-      float nw0[NKB], nw1[NKB];
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) { nw0[kb] = wr[cn * kp + woff[kb]]; nw1[kb] = wr[(cn + 4) * kp + woff[kb]]; }
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[kb], x0, acc[kb], 0, 0, 0);
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) acc[kb] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[kb], x1, acc[kb], 0, 0, 0);
-      x0 = nx0; x1 = nx1;
-#pragma unroll
-      for (int kb = 0; kb < NKB; ++kb) { w0[kb] = nw0[kb]; w1[kb] = nw1[kb]; }
-    }
+    f32x4 acc[NKB], accd;
+    band_scores<NKB, false>(xl + (wave * 16 + col) * ldx + kq, wl + kq * kp, rows, cs, acc, accd);
     const long long pix = tile * PROJ_TILE + wave * 16 + col;
     if (pix < P) {
 #pragma unroll
@@ -371,8 +319,7 @@ static inline size_t band_gram_bytes(int cs) {
   return (size_t)BAND_GRAM_PARTS * (nb * (nb + 1) / 2) * 1024 * 8;
 }
 static inline size_t band_project_lds(int cs, int ks) {
-  const int nkb = (ks + 15) / 16, kp = (nkb * 16 + 31) & ~31, ldx = cs + 2 + ((32 - (cs & 31)) & 31);
-  return ((size_t)cs * kp + (size_t)PROJ_TILE * ldx) * 4;
+  return ((size_t)cs * band_kp((ks + 15) / 16) + (size_t)PROJ_TILE * band_tile_stride(cs)) * 4;
 }
 
 extern "C" int hpri_band_fp32_run(void) { return BAND_FP32_RUN; }
@@ -381,7 +328,7 @@ extern "C" int hpri_band_project_max_k(void) { return PROJ_MAX_K; }
 
 // 0 for a channel stride the family does not take
 extern "C" size_t hpri_band_workspace_bytes(int cs) {
-  if (cs <= 0 || cs % 8 != 0 || cs > BAND_MAX_CS) return 0;
+  if (!band_cs_ok(cs)) return 0;
   const size_t a = band_moment_bytes(cs), b = band_gram_bytes(cs);
   return a > b ? a : b;
 }
@@ -455,7 +402,7 @@ extern "C" int hpri_band_project(const float* x, long long pixels, int cs, const
                                  hipStream_t stream) {
   HPRI_REQUIRE(x && weight && bias && y, "band_project: null pointer");
   HPRI_REQUIRE(pixels > 0 && K > 0, "band_project: bad sizes");
-  HPRI_REQUIRE(cs > 0 && cs % 8 == 0 && cs <= BAND_MAX_CS, "band_project: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
+  HPRI_REQUIRE(band_cs_ok(cs), "band_project: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
   HPRI_REQUIRE(K <= PROJ_MAX_K, "band_project: K exceeds hpri_band_project_max_k");
   const int ks = (K + 7) & ~7;
   const size_t lds = band_project_lds(cs, ks);
@@ -464,13 +411,9 @@ extern "C" int hpri_band_project(const float* x, long long pixels, int cs, const
   const long long tiles = (pixels + PROJ_TILE - 1) / PROJ_TILE;
   const long long per_cu = BAND_LDS_BYTES / (long long)lds;
   const dim3 grid = cache_grid(tiles, (int)(per_cu < 1 ? 1 : per_cu > 4 ? 4 : per_cu));
-  // (more than 64 KB of dynamic LDS has to be asked for, per device; a runtime that needs no such request may refuse it: the launch
-  // reports what matters)
 #define BAND_PROJECT_LAUNCH(NKB_)                                                                                                  \
   do {                                                                                                                             \
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)band_project_kernel<NKB_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                               (int)lds) != hipSuccess)                                                            \
-      (void)hipGetLastError();                                                                                                     \
+    hpri_ask_dynamic_lds(band_project_kernel<NKB_>, lds);                                                                          \
     hipLaunchKernelGGL(band_project_kernel<NKB_>, grid, dim3(BAND_THREADS), lds, stream, x, pixels, cs / 4, weight, bias, ks, y);  \
   } while (0)
   switch ((ks + 15) / 16) {                            // blocks of 16 output channels

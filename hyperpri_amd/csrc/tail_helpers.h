@@ -1,5 +1,5 @@
 // The rules the kernels of a step's tail share (step.hip, segmap.hip, multiclass.hip, segloss.hip, components.hip, distance.hip,
-// skeleton.hip, spectral.hip, sort.hip and the cube cache's launchers): every rule once.  They carry the reproducibility promise -- fp64 sums
+// skeleton.hip, sort.hip, guided.hip, ridge.hip, the band family and the cube cache's launchers): every rule once.  They carry the reproducibility promise -- fp64 sums
 // in a fixed order, fixed butterflies, integer atomics only -- so a new tail kernel takes them from here and restates none of them.
 #pragma once
 #include "common.h"
@@ -28,7 +28,23 @@ static inline int hpri_grid_capped(long long items, int per_block) {
 // every pointer 16-byte aligned (a null pointer is)
 template <typename... P> static inline bool hpri_aligned16(P... ptr) { return ((((uintptr_t)ptr) | ...) & 15) == 0; }
 
+// ---- host: a launch with more than 64 KB of dynamic LDS -------------------------------------------------------------------------
+// More than 64 KB has to be asked for, per kernel and device; a runtime that needs no such request may refuse it, and the refusal is
+// forgotten: the launch reports what matters.
+template <class K> static inline void hpri_ask_dynamic_lds(K kernel, size_t bytes) {
+  if (bytes > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+    (void)hipGetLastError();
+}
+
 #ifdef __HIPCC__
+// ---- the logit of a score in [0, 1], clamped to [2^-24, 1 - 2^-24]: finite for every input, NaN aside -------------------------------
+#define HPRI_P_LO 5.9604644775390625e-08f    // 2^-24
+#define HPRI_P_HI 0.99999994039535522f       // 1 - 2^-24
+__device__ __forceinline__ float hpri_clamped_logit(float s) {
+  const float p = fminf(fmaxf(s, HPRI_P_LO), HPRI_P_HI);
+  return logf(p) - log1pf(-p);
+}
+
 // ---- a wave's 64 lanes: xor butterfly 32 .. 1, the result in every lane ------------------------------------------------------------
 template <typename T> __device__ __forceinline__ T hpri_wave_sum(T v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

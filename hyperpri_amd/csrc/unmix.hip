@@ -11,8 +11,8 @@
 // include/hyperpri_hip.h states the modes and the active-set rule in full.
 //
 // Layout.  A workgroup is four waves and owns one tile of UM_TILE = 64 pixels at a time (a persistent grid of two workgroups per CU
-// -- one where two tiles do not fit the LDS).  The tile sits in LDS as band_detect_kernel keeps it (rows at band_tile_stride(cs),
-// written as 8-byte pairs); the 16 basis rows (15 KB at cs = 240) are streamed from L2 as band_detect_kernel streams its weight: a
+// -- one where two tiles do not fit the LDS).  The tile sits in LDS as band_common.h keeps it (band_tile_load, band_tile_stage: rows at
+// band_tile_stride(cs), written as 8-byte pairs); the 16 basis rows (15 KB at cs = 240) are streamed from L2, not staged: a
 // lane's consecutive k-steps walk one cache line.  v_mfma_f32_16x16x4_f32: wave w multiplies the 16 rows against its 16 pixels;
 // lane l holds A[i = l & 15][k = l >> 4] = Q32[i][c + k] and B[k][j = l & 15] = x[pixel 16 w + j][c + k]; D: column (pixel) = l & 15,
 // row = 4 (l >> 4) + reg.  y goes to LDS.
@@ -43,34 +43,10 @@
 #define UM_LOADERS (UM_THREADS - 64)    // unmix: the waves 1 .. 3 fetch
 #define UM_LOADS ((UM_TILE * (BAND_MAX_CS / 4) + UM_LOADERS - 1) / UM_LOADERS)
 #define UM_XLOADS ((UM_TILE * (BAND_MAX_CS / 4) + UM_THREADS - 1) / UM_THREADS)
-#define UM_P_LO 5.9604644775390625e-08f     // 2^-24: the clamp of detect.hip's logit
-#define UM_P_HI 0.99999994039535522f        // 1 - 2^-24
 #define UM_TAU 9.094947017729282e-13        // 2^-40
 #define UM_PARTIALS HPRI_MAX_BLOCKS         // the most workgroups of the ATGP pass: the workspace holds one (v, position) each
 
-__device__ __forceinline__ float um_logit(float s) {
-  const float p = fminf(fmaxf(s, UM_P_LO), UM_P_HI);
-  return logf(p) - log1pf(-p);
-}
-
 // ---- what the two kernels share ----------------------------------------------------------------------------------------------------
-// quads held in registers -> the tile in LDS (8-byte pairs); the quad index is hidden from the optimiser per tile by the caller
-template <typename V, int LOADS, int THREADS>
-__device__ __forceinline__ void um_stage(float* __restrict__ xl, const V (&v)[LOADS], int lt, int ql, int ldx) {
-  const int total = UM_TILE * ql;
-#pragma unroll
-  for (int u = 0; u < LOADS; ++u) {
-    const int idx = lt + u * THREADS;
-    if (idx < total) {
-      const int px = idx / ql, cq = idx - px * ql;
-      const f32x4 w = band_widen(v[u]);
-      float2* d = reinterpret_cast<float2*>(xl + px * ldx + 4 * cq);
-      d[0] = float2{w[0], w[1]};
-      d[1] = float2{w[2], w[3]};
-    }
-  }
-}
-
 // the 16 basis rows against the 16 pixels of this wave; two k-steps per iteration (cs % 8 == 0), the operands of the next iteration
 // read before this one's MFMAs issue (the last iteration reads its own again).  (A queue that keeps the basis operands six
 // iterations ahead measured slower, DESIGN.md.)
@@ -298,24 +274,16 @@ __device__ __forceinline__ unsigned um_tiles(const UmArgs& g, float* __restrict_
   const int lt = t - 64;                               // a loader's index
   unsigned ncap = 0;
   f32x4 v[SOLVER ? 1 : UM_LOADS];
-  // (q4 is hidden from the optimiser per tile, as band_detect_kernel hides it)
-  int ql = g.q4;
+  int ql = g.q4;                                       // (hidden from the optimiser per tile: band_tile_stage)
   auto load = [&](long long tile) {
-    const long long p0 = tile * UM_TILE;
-    const float* src = g.x + p0 * cs;
-    const int left = (int)min((long long)UM_TILE, g.P - p0) * ql;    // quads of the tile that lie inside the batch
-#pragma unroll
-    for (int u = 0; u < (SOLVER ? 0 : UM_LOADS); ++u) {
-      const int idx = lt + u * UM_LOADERS;
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (idx < left) v[u] = *reinterpret_cast<const f32x4*>(src + 4 * idx);
-    }
+    const long long p0 = tile * UM_TILE;               // (left: the quads of the tile that lie inside the batch)
+    band_tile_load<(SOLVER ? 1 : UM_LOADS), UM_LOADERS>(v, g.x + p0 * cs, lt, (int)min((long long)UM_TILE, g.P - p0) * ql);
   };
   if (!SOLVER && blockIdx.x < tiles) load(blockIdx.x);
   for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     __syncthreads();                                   // (the previous tile has been consumed)
     asm volatile("" : "+s"(ql));
-    if (!SOLVER) um_stage<f32x4, (SOLVER ? 1 : UM_LOADS), UM_LOADERS>(xl, v, lt, ql, ldx);
+    if (!SOLVER) band_tile_stage<(SOLVER ? 1 : UM_LOADS), UM_LOADERS>(xl, v, lt, UM_TILE * ql, ql, ldx, BandQuadAsIs());
     __syncthreads();
     {
       const int px = wave * 16 + col;
@@ -338,7 +306,7 @@ __device__ __forceinline__ unsigned um_tiles(const UmArgs& g, float* __restrict_
         if (pix < g.P) g.abund[(long long)m * g.P + pix] = a32;
         if ((g.fg >> m) & 1u) f += a32;
       }
-      if (g.value != nullptr && pix < g.P) g.value[pix] = um_logit(f);
+      if (g.value != nullptr && pix < g.P) g.value[pix] = hpri_clamped_logit(f);
     } else if (tile + gridDim.x < tiles) {
       load(tile + gridDim.x);
     }
@@ -396,14 +364,7 @@ __global__ __launch_bounds__(UM_THREADS, 2) void band_extreme_kernel(const T* __
     long long base, pos;
     int npix;
     place(tile, base, npix, pos);
-    const T* src = cache + base * cs;
-    const int left = npix * ql;
-#pragma unroll
-    for (int u = 0; u < UM_XLOADS; ++u) {
-      const int idx = t + u * UM_THREADS;
-      v[u] = decltype(band_raw(cache)){};
-      if (idx < left) v[u] = band_raw(src + 4 * idx);
-    }
+    band_tile_load<UM_XLOADS, UM_THREADS>(v, cache + base * cs, t, npix * ql);
   };
   float bv = 0.f;
   long long bpos = -1;
@@ -411,7 +372,7 @@ __global__ __launch_bounds__(UM_THREADS, 2) void band_extreme_kernel(const T* __
   for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     __syncthreads();
     asm volatile("" : "+s"(ql));
-    um_stage<decltype(band_raw(cache)), UM_XLOADS, UM_THREADS>(xl, v, t, ql, ldx);
+    band_tile_stage<UM_XLOADS, UM_THREADS>(xl, v, t, UM_TILE * ql, ql, ldx, BandQuadAsIs());
     __syncthreads();
     if (tile + gridDim.x < tiles) load(tile + gridDim.x);
     if (K > 0) {
@@ -461,14 +422,6 @@ static inline size_t um_lds_bytes(int cs) {
   return ((size_t)UM_TILE * band_tile_stride(cs) + 2 * (size_t)UM_MAX_M * UM_TILE) * 4;
 }
 
-// (more than 64 KB of dynamic LDS has to be asked for, per device; a runtime that needs no such request may refuse it: the launch
-// reports what matters)
-#define UM_ASK_LDS(kernel_, lds_)                                                                                                  \
-  do {                                                                                                                             \
-    if ((lds_) > 64 * 1024 && hipFuncSetAttribute((const void*)kernel_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_)) != hipSuccess) \
-      (void)hipGetLastError();                                                                                                     \
-  } while (0)
-
 extern "C" int hpri_band_unmix_max_members(void) { return UM_MAX_M; }
 
 extern "C" int hpri_band_unmix(const float* x, long long pixels, int cs, int C, const float* basis, const float* members,
@@ -476,7 +429,7 @@ extern "C" int hpri_band_unmix(const float* x, long long pixels, int cs, int C, 
                                float* value, unsigned long long* capped, hipStream_t stream) {
   HPRI_REQUIRE(x && basis && members && tri && abundances && capped, "band_unmix: null pointer");
   HPRI_REQUIRE(pixels > 0, "band_unmix: bad sizes");
-  HPRI_REQUIRE(cs > 0 && cs % 8 == 0 && cs <= BAND_MAX_CS, "band_unmix: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
+  HPRI_REQUIRE(band_cs_ok(cs), "band_unmix: the channel stride must be a multiple of 8 up to hpri_band_max_cs");
   HPRI_REQUIRE(M > 0 && M <= UM_MAX_M, "band_unmix: M must lie in [1, hpri_band_unmix_max_members]");
   HPRI_REQUIRE(C >= M && C <= cs, "band_unmix: the band count must lie in [M, cs]");
   HPRI_REQUIRE(mode >= 0 && mode <= 3, "band_unmix: mode must be 0 (ucls), 1 (scls), 2 (ncls) or 3 (fcls)");
@@ -491,12 +444,12 @@ extern "C" int hpri_band_unmix(const float* x, long long pixels, int cs, int C, 
   const UmArgs g = {x, pixels, cs / 4, basis, members, tri, mode, cap == 0 ? 3 * M : cap, (unsigned)foreground, C, abundances, rmse, value};
 #define UM_LAUNCH(M_)                                                                                                              \
   case M_:                                                                                                                         \
-    UM_ASK_LDS(band_unmix_kernel<M_>, lds);                                                                                        \
+    hpri_ask_dynamic_lds(band_unmix_kernel<M_>, lds);                                                                              \
     hipLaunchKernelGGL(band_unmix_kernel<M_>, grid, dim3(UM_THREADS), lds, stream, g, capped);                                      \
     break
   switch (M) {
     UM_LAUNCH(1); UM_LAUNCH(2); UM_LAUNCH(3); UM_LAUNCH(4); UM_LAUNCH(5); UM_LAUNCH(6); UM_LAUNCH(7);
-    default: UM_ASK_LDS(band_unmix_kernel<8>, lds); hipLaunchKernelGGL(band_unmix_kernel<8>, grid, dim3(UM_THREADS), lds, stream, g, capped); break;
+    default: hpri_ask_dynamic_lds(band_unmix_kernel<8>, lds); hipLaunchKernelGGL(band_unmix_kernel<8>, grid, dim3(UM_THREADS), lds, stream, g, capped); break;
   }
 #undef UM_LAUNCH
   HPRI_CHECK_LAUNCH();
@@ -521,11 +474,11 @@ extern "C" int hpri_band_extreme(const void* cache, int cache_dtype, int slots, 
   if (grid.x > UM_PARTIALS) grid.x = UM_PARTIALS;
   UmBest* part = (UmBest*)workspace;
   if (cache_dtype == 0) {
-    UM_ASK_LDS(band_extreme_kernel<float>, lds);
+    hpri_ask_dynamic_lds(band_extreme_kernel<float>, lds);
     hipLaunchKernelGGL(band_extreme_kernel<float>, grid, dim3(UM_THREADS), lds, stream, (const float*)cache, masks, slot_table, slots, P,
                        cs / 4, tps, tiles, select, basis, K, part);
   } else {
-    UM_ASK_LDS(band_extreme_kernel<_Float16>, lds);
+    hpri_ask_dynamic_lds(band_extreme_kernel<_Float16>, lds);
     hipLaunchKernelGGL(band_extreme_kernel<_Float16>, grid, dim3(UM_THREADS), lds, stream, (const _Float16*)cache, masks, slot_table,
                        slots, P, cs / 4, tps, tiles, select, basis, K, part);
   }

@@ -98,6 +98,48 @@ def _names(index, n: int) -> List[object]:
     return names
 
 
+class _SplitStore:
+    """What the ``*_split`` loops keep per batch and hand over as a ``SplitPrediction``.  ``add_mask`` copies the batch's mask and records
+    the names, offsets and sizes of its ``n`` images; the flat logits go into ``logits`` beside it -- apart, because ``predict_split``
+    under TTA must store the mask before the views run.  ``add_scores`` does both for a baseline's score map."""
+
+    def __init__(self) -> None:
+        self.logits: List[torch.Tensor] = []
+        self.masks: List[torch.Tensor] = []
+        self.spreads: List[torch.Tensor] = []
+        self.offsets, self.sizes, self.names = [0], [], []
+
+    def add_mask(self, mask: torch.Tensor, index, n: int, h: int, w: int) -> None:
+        self.masks.append(mask.to(torch.float32).reshape(-1).clone())
+        self.names.extend(_names(index, n))
+        for _ in range(n):
+            self.offsets.append(self.offsets[-1] + h * w)
+            self.sizes.append((h, w))
+
+    def add_scores(self, pred: torch.Tensor, batch: dict, clone: bool = True) -> None:
+        """One (N, h, w) score map of a baseline against ``batch['mask']``."""
+        mask = batch["mask"]
+        n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
+        if mask.numel() != n * h * w:
+            raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
+                             f"and a mask {tuple(mask.shape)}")
+        self.logits.append(pred.reshape(-1).clone() if clone else pred.reshape(-1))
+        self.add_mask(mask, batch.get("index"), n, h, w)
+
+    def result(self, who: str) -> SplitPrediction:
+        if not self.logits:
+            raise ValueError(f"{who}: no batches")
+        return SplitPrediction(torch.cat(self.logits), torch.cat(self.masks), self.offsets, self.sizes, self.names,
+                               torch.cat(self.spreads) if self.spreads else None)
+
+
+def _checked_batch(batch: dict) -> Tuple[torch.Tensor, torch.Tensor]:
+    image, mask = batch["image"], batch["mask"]
+    _require_cuda(image, "evaluation image")
+    _require_device(mask, "evaluation mask")
+    return image, mask
+
+
 def tta_merge(view_logits: Sequence[torch.Tensor], views: Sequence[str], merge: str = "prob", spread: bool = False,
               frame: Optional[Tuple[int, int]] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """One ``hpri_tta_merge`` launch (csrc/tta.hip; the contract is restated by ``tta.tta_merge_reference``): ``view_logits[v]`` is
@@ -179,10 +221,7 @@ def predict_split(network: nn.Module, batches: Iterable[dict], tta: Optional[TTA
     if tta is not None and not isinstance(tta, TTA):
         raise TypeError(f"predict_split: tta must be a hyperpri_amd.TTA or None, got {type(tta).__name__}")
     was_training = network.training
-    spreads: List[torch.Tensor] = []
-    logits: List[torch.Tensor] = []
-    masks: List[torch.Tensor] = []
-    offsets, sizes, names = [0], [], []
+    store = _SplitStore()
     network.eval()
     try:
         with torch.inference_mode():
@@ -193,21 +232,18 @@ def predict_split(network: nn.Module, batches: Iterable[dict], tta: Optional[TTA
                     if mask.dim() < 2:
                         raise ValueError(f"evaluate: need a (N, 1, h, w) or (N, h, w) mask, got {tuple(mask.shape)}")
                     h, w = int(mask.shape[-2]), int(mask.shape[-1])
-                    # first of all: the views below rotate through the output slots the mask lives in
-                    masks.append(mask.to(torch.float32).reshape(-1).clone())
                     n = mask.numel() // (h * w)
-                    names.extend(_names(batch.get("index"), n))
+                    # first of all: the views below rotate through the output slots the mask lives in
+                    store.add_mask(mask, batch.get("index"), n, h, w)
                     views = _view_logits(network, batch, tta, 1, (h, w), "predict_split")
                     if int(views[0].shape[0]) != n:
                         raise ValueError(f"evaluate: {int(views[0].shape[0])} images of logits for {n} masks")
                     merged, sp = tta_merge(views, tta.views, tta.merge, tta.spread, (h, w))
-                    logits.append(merged.reshape(-1))
+                    store.logits.append(merged.reshape(-1))
                     if sp is not None:
-                        spreads.append(sp.reshape(-1))
+                        store.spreads.append(sp.reshape(-1))
                 else:
-                    image, mask = batch["image"], batch["mask"]
-                    _require_cuda(image, "evaluation image")
-                    _require_device(mask, "evaluation mask")
+                    image, mask = _checked_batch(batch)
                     pred = network(image)
                     if isinstance(pred, tuple):                  # analyze=True networks return (pred, features)
                         pred = pred[0]
@@ -217,15 +253,9 @@ def predict_split(network: nn.Module, batches: Iterable[dict], tta: Optional[TTA
                         raise ValueError(f"evaluate: need one logit and one mask value per pixel, got logits {tuple(pred.shape)} "
                                          f"and a mask {tuple(mask.shape)}")
                     # copies: a cache hands out views of buffers it rewrites two batches later
-                    logits.append(pred.detach().to(torch.float32).reshape(-1).clone())
-                    masks.append(mask.to(torch.float32).reshape(-1).clone())
-                    names.extend(_names(batch.get("index"), n))
-                for _ in range(n):
-                    offsets.append(offsets[-1] + h * w)
-                    sizes.append((h, w))
-            if not logits:
-                raise ValueError("predict_split: no batches")
-            return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, torch.cat(spreads) if spreads else None)
+                    store.logits.append(pred.detach().to(torch.float32).reshape(-1).clone())
+                    store.add_mask(mask, batch.get("index"), n, h, w)
+            return store.result("predict_split")
     finally:
         network.train(was_training)
 
@@ -235,87 +265,39 @@ def detect_split(detector: nn.Module, batches: Iterable[dict], score: str = "ace
     the detector's ``logit=True`` map of ``score`` for target ``target`` (``rx`` has one map) is stored as ``logits`` -- copied, as
     the cache rewrites its output slots -- with masks, offsets, sizes and names exactly as ``predict_split`` stores them, so
     ``validate_net``, ``test_net``, ``write_segmaps``, ``clean_prediction``, ``surface_metrics`` and the rest read it unchanged."""
-    logits: List[torch.Tensor] = []
-    masks: List[torch.Tensor] = []
-    offsets, sizes, names = [0], [], []
+    store = _SplitStore()
     with torch.inference_mode():
         for batch in batches:
-            image, mask = batch["image"], batch["mask"]
-            _require_cuda(image, "evaluation image")
-            _require_device(mask, "evaluation mask")
+            image, _ = _checked_batch(batch)
             maps = detector(image, score=score, logit=True)
             if not 0 <= int(target) < int(maps.shape[1]):
                 raise ValueError(f"detect_split: target {target} of a detector with {int(maps.shape[1])} map(s)")
-            pred = maps[:, int(target)]
-            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
-            if mask.numel() != n * h * w:
-                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
-                                 f"and a mask {tuple(mask.shape)}")
-            logits.append(pred.reshape(-1).clone())
-            masks.append(mask.to(torch.float32).reshape(-1).clone())
-            names.extend(_names(batch.get("index"), n))
-            for _ in range(n):
-                offsets.append(offsets[-1] + h * w)
-                sizes.append((h, w))
-        if not logits:
-            raise ValueError("detect_split: no batches")
-        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+            store.add_scores(maps[:, int(target)], batch)
+        return store.result("detect_split")
 
 
 def cluster_split(model: nn.Module, batches: Iterable[dict]) -> SplitPrediction:
     """``detect_split`` for a clustering (``hyperpri_amd.SpectralKMeans`` after ``calibrate``): per batch the model's ``"logit"`` map --
     the logit of the foreground share of every pixel's cluster -- is stored as ``logits``, with masks, offsets, sizes and names
     exactly as ``predict_split`` stores them, so the evaluation functions read an unsupervised baseline unchanged."""
-    logits: List[torch.Tensor] = []
-    masks: List[torch.Tensor] = []
-    offsets, sizes, names = [0], [], []
+    store = _SplitStore()
     with torch.inference_mode():
         for batch in batches:
-            image, mask = batch["image"], batch["mask"]
-            _require_cuda(image, "evaluation image")
-            _require_device(mask, "evaluation mask")
-            pred = model(image, output="logit")[:, 0]
-            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
-            if mask.numel() != n * h * w:
-                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
-                                 f"and a mask {tuple(mask.shape)}")
-            logits.append(pred.reshape(-1).clone())
-            masks.append(mask.to(torch.float32).reshape(-1).clone())
-            names.extend(_names(batch.get("index"), n))
-            for _ in range(n):
-                offsets.append(offsets[-1] + h * w)
-                sizes.append((h, w))
-        if not logits:
-            raise ValueError("cluster_split: no batches")
-        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+            image, _ = _checked_batch(batch)
+            store.add_scores(model(image, output="logit")[:, 0], batch)
+        return store.result("cluster_split")
 
 
 def unmix_split(model: nn.Module, batches: Iterable[dict], mode: str = "fcls") -> SplitPrediction:
     """``cluster_split`` for an unmixer (``hyperpri_amd.SpectralUnmixer`` with a foreground endmember): per batch the model's ``"logit"``
     map under ``mode`` -- the logit of every pixel's foreground abundance -- is stored as ``logits``, with masks, offsets, sizes and
     names exactly as ``predict_split`` stores them, so the evaluation functions read a soft baseline unchanged."""
-    logits: List[torch.Tensor] = []
-    masks: List[torch.Tensor] = []
-    offsets, sizes, names = [0], [], []
+    store = _SplitStore()
     with torch.inference_mode():
         for batch in batches:
-            image, mask = batch["image"], batch["mask"]
-            _require_cuda(image, "evaluation image")
-            _require_device(mask, "evaluation mask")
-            pred = model(image, mode=mode, output="logit")[:, 0]
-            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
-            if mask.numel() != n * h * w:
-                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
-                                 f"and a mask {tuple(mask.shape)}")
-            logits.append(pred.reshape(-1).clone())
-            masks.append(mask.to(torch.float32).reshape(-1).clone())
-            names.extend(_names(batch.get("index"), n))
-            for _ in range(n):
-                offsets.append(offsets[-1] + h * w)
-                sizes.append((h, w))
-        if not logits:
-            raise ValueError("unmix_split: no batches")
-        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+            image, _ = _checked_batch(batch)
+            store.add_scores(model(image, mode=mode, output="logit")[:, 0], batch)
+        return store.result("unmix_split")
 
 
 def refine_split(pred: SplitPrediction, batches: Iterable[dict], guide, radius: int, eps: float, domain: str = "prob") -> SplitPrediction:
@@ -357,33 +339,18 @@ def ridge_split(batches: Iterable[dict], plane, sigmas, **ridge) -> SplitPredict
     from .ridge import ridge_filter
     if "output" in ridge or "return_scale" in ridge or "return_hessian" in ridge:
         raise ValueError("ridge_split: it stores output='logit' of the response; output, return_scale and return_hessian are not its to take")
-    logits: List[torch.Tensor] = []
-    masks: List[torch.Tensor] = []
-    offsets, sizes, names = [0], [], []
+    store = _SplitStore()
     with torch.inference_mode():
         for batch in batches:
-            image, mask = batch["image"], batch["mask"]
-            _require_cuda(image, "evaluation image")
-            _require_device(mask, "evaluation mask")
+            image, _ = _checked_batch(batch)
             maps = plane(image)
             if maps.dim() == 5 and maps.shape[1] == 1:
                 maps = maps[:, 0]
             if maps.dim() != 4:
                 raise ValueError(f"ridge_split: the plane must be (N, T, h, w) or (N, 1, T, h, w), got {tuple(maps.shape)}")
-            pred = ridge_filter(maps[:, :1], sigmas, output="logit", **ridge)[:, 0]
-            n, h, w = int(pred.shape[0]), int(pred.shape[-2]), int(pred.shape[-1])
-            if mask.numel() != n * h * w:
-                raise ValueError(f"evaluate: need one score and one mask value per pixel, got scores {tuple(pred.shape)} "
-                                 f"and a mask {tuple(mask.shape)}")
-            logits.append(pred.reshape(-1))
-            masks.append(mask.to(torch.float32).reshape(-1).clone())
-            names.extend(_names(batch.get("index"), n))
-            for _ in range(n):
-                offsets.append(offsets[-1] + h * w)
-                sizes.append((h, w))
-        if not logits:
-            raise ValueError("ridge_split: no batches")
-        return SplitPrediction(torch.cat(logits), torch.cat(masks), offsets, sizes, names, None)
+            # (a fresh tensor of the filter's own: stored without a copy)
+            store.add_scores(ridge_filter(maps[:, :1], sigmas, output="logit", **ridge)[:, 0], batch, clone=False)
+        return store.result("ridge_split")
 
 
 def enhance_split(pred: SplitPrediction, sigmas, **ridge) -> SplitPrediction:

@@ -434,3 +434,42 @@ def test_module_outputs_and_layout_paths():
     real[0, 0, 0, :] = np.nan
     y = model(torch.from_numpy(np.ascontiguousarray(real.transpose(0, 3, 1, 2))).to(DEV))
     assert int(y.max()) < K
+
+
+# ---- the scores are the projection's chain, bit for bit ----------------------------------------------------------------
+def _project(x, W, b):
+    """``hpri_band_project`` itself on a (P, cs) fp32 device buffer: the (P, K) outputs of the rows ``W`` (K, C), ``b`` (K,).  A row's
+    chain involves no other row, so where the launcher refuses all K rows at once (at cs = 320 sixty-four rows and its tile of 64
+    pixels do not fit the LDS together) the rows go through it 32 at a time."""
+    from hyperpri_amd import _lib
+    from hyperpri_amd._args import _p, _stream
+    P, cs = int(x.shape[0]), int(x.shape[1])
+    K = int(W.shape[0])
+    fits = (cs * _rup(_rup(K, 16), 32) + 64 * (_rup(cs, 32) + 2)) * 4 <= 160 * 1024
+    out = []
+    for k0 in range(0, K, K if fits else 32):
+        k1 = min(K, k0 + (K if fits else 32))
+        wd, bd = _rows(W[k0:k1], b[k0:k1], cs)
+        y = torch.full((P, _rup(k1 - k0, 8)), float("nan"), dtype=torch.float32, device=DEV)
+        _lib.call("hpri_band_project", _p(x), P, cs, _p(wd), _p(bd), k1 - k0, _p(y), _stream())
+        torch.cuda.synchronize()
+        out.append(y.cpu().numpy()[:, :k1 - k0])
+    return np.concatenate(out, axis=1)
+
+
+@pytest.mark.parametrize("C,K,sizes", [(37, 6, (65, 130)), (37, 33, (65, 130)), (313, 64, (70,))])
+def test_assign_scores_are_bitwise_the_projection_chain(C, K, sizes):
+    """The head of cluster.hip: z[k] is "bitwise the chain of hpri_band_project".  On seeded normal fp32 pixels (no pivot, random W
+    and b) ``zmin`` equals the minimum over k < K of the projection's output on the same buffer and rows, bit for bit, and ``labels``
+    is the lowest index of that minimum.  K = 6 is one block of 16 rows, K = 33 three; 65 and 130 pixels leave a ragged second tile;
+    (313, 64) is cs = 320, where the assign tile is 32 pixels and two waves score."""
+    cs = _rup(C, 8)
+    rng = np.random.RandomState(1000 * C + K)
+    W, b = rng.randn(K, C).astype(np.float32), rng.randn(K).astype(np.float32)
+    for P in sizes:
+        x = _padded(rng.randn(P, C).astype(np.float32), cs)
+        z = _project(x, W, b)
+        got = _assign(x, None, W, b, outputs=("labels", "zmin"))
+        assert z.shape == (P, K) and np.isfinite(z).all()
+        assert np.array_equal(got["zmin"].view(np.uint32), z.min(axis=1).view(np.uint32)), (C, K, P)
+        assert np.array_equal(got["labels"].astype(np.int64), z.argmin(axis=1)), (C, K, P)
