@@ -447,7 +447,8 @@ static int g3_launch(int mode, const void* xp, int x_cs, int x_coff, const void*
   }
   HPRI_REQUIRE(!(a.accumulate && mode == 1), "gemm_bf16v3: the depth-to-space form does not accumulate");
   if (mode == 0 || mode == 2) {
-    HPRI_REQUIRE(y_cw % 4 == 0 && y_cw >= Ncols && y_cw <= ((Ncols_pad + G3_BN - 1) / G3_BN) * G3_BN, "gemm_bf16v3: written width must be a multiple of 4 in [Ncols, column blocks]");
+    // (columns beyond the pack multiply a clamped packed row: they hold no zeros and must stay unwritten)
+    HPRI_REQUIRE(y_cw % 4 == 0 && y_cw >= Ncols && y_cw <= Ncols_pad, "gemm_bf16v3: written width must be a multiple of 4 in [Ncols, Ncols_pad]");
     if (y != nullptr) HPRI_REQUIRE(y_cw + y_coff <= y_cs, "gemm_bf16v3: written width exceeds the fp32 row stride");
     if (y16 != nullptr) HPRI_REQUIRE(y_cw + y16_coff <= y16_cs, "gemm_bf16v3: written width exceeds the bf16 row stride");
     HPRI_REQUIRE(stats == nullptr || (mode == 0 && stat_cp >= Ncols && !a.accumulate), "gemm_bf16v3: statistics only for plain, non-accumulating launches");

@@ -268,7 +268,7 @@ int hpri_convt_dgrad_f32v2(const float* dy, int dy_cs, int dy_coff, const float*
  * (models.py:105-115,143; model_parts.py:96) and ConvTranspose2d(k=2,s=2) forward / data gradient (model_parts.py:63-64).
  * hpri_gemm_bf16v3: y[p, n] (+)= sum_k x[p, k] w[n, k] + bias[n]; x = bf16 planes of N*HW rows (x_cs elements per row, K_pad read
  * from x_coff on), w = hpri_pack_weight_bf16 with T = 1 (modes 0 / 1); outputs fp32 view y and / or bf16 view y16 (either may be
- * NULL), y_cw columns written; accumulate bit 0: add to y, bit 1: ReLU; stats: one record row of stat_cp columns per 256-row tile
+ * NULL), y_cw columns written (a multiple of 4 in [Ncols, Ncols_pad]); accumulate bit 0: add to y, bit 1: ReLU; stats: one record row of stat_cp columns per 256-row tile
  * (hpri_gemm_bf16v3_plan; tiles never straddle images) for hpri_bn_finalize.
  * hpri_convt_fwd_bf16v3: column tap*Cup + co (pack mode 2) -> pixel (py0 + 2y + tap/2, px0 + 2x + tap%2), channel co of the
  * [N, H2, W2] views; Cup % 16 == 0.  hpri_convt_dgrad_bf16v3: dx (+)= gather over the four parities of the dy planes (pack mode 3,
