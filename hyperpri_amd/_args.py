@@ -136,11 +136,37 @@ def _ignore_args(ignore_index: Optional[int]) -> Tuple[int, int]:
 FILTER_DOMAINS = ("linear", "prob")
 
 
+def _int_arg(v, lo: int, hi: int, what: str, who: str) -> int:
+    """An integer parameter of a windowed filter (a radius, a number of iterations) in [lo, hi]; a bool is none."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or not lo <= int(v) <= hi:
+        raise ValueError(f"{who}: {what} must be an integer in [{lo}, {hi}], got {v!r}")
+    return int(v)
+
+
+def _weight_arg(v, what: str, who: str) -> float:
+    """A weight as the fp32 value a launch receives: non-negative and finite."""
+    x = float(np.float32(_scalar(v, f"{who}: {what}")))
+    if not (x >= 0.0 and np.isfinite(x)):
+        raise ValueError(f"{who}: {what} must be non-negative and finite as an fp32 value, got {v!r}")
+    return x
+
+
+def _guide_frame(guide: torch.Tensor, max_guides: int, who: str, min_guides: int = 1) -> torch.Tensor:
+    """A guide (N, K, h, w) or (N, 1, K, h, w) with K in [min_guides, max_guides] -> its 4-d view."""
+    g = guide
+    if g.dim() == 5:
+        if g.shape[1] != 1:
+            raise ValueError(f"{who}: a 5-d guide must be (N, 1, K, h, w), got {tuple(g.shape)}")
+        g = g[:, 0]
+    if g.dim() != 4 or not min_guides <= int(g.shape[1]) <= max_guides:
+        raise ValueError(f"{who}: need a guide (N, K, h, w) or (N, 1, K, h, w) with K in [{min_guides}, {max_guides}], got {tuple(guide.shape)}")
+    return g
+
+
 def _filter_args(radius, eps, domain, max_radius: int, who: str) -> Tuple[int, float, int]:
     """The parameters of an edge-preserving filter as its kernels take them: (radius in [1, max_radius], eps as the fp32 value the
     launch receives -- positive and finite --, the code of ``domain``)."""
-    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= max_radius:
-        raise ValueError(f"{who}: radius must be an integer in [1, {max_radius}], got {radius!r}")
+    _int_arg(radius, 1, max_radius, "radius", who)
     e = float(np.float32(_scalar(eps, f"{who}: eps")))
     if not (e > 0.0 and np.isfinite(e)):
         raise ValueError(f"{who}: eps must be positive and finite as an fp32 value, got {eps!r}")

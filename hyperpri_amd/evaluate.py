@@ -330,6 +330,39 @@ def refine_split(pred: SplitPrediction, batches: Iterable[dict], guide, radius: 
     return SplitPrediction(torch.cat(logits), pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
 
 
+def crf_split(pred: SplitPrediction, batches: Iterable[dict], guide, **crf) -> SplitPrediction:
+    """``refine_split`` for the dense CRF (``hyperpri_amd.dense_crf``, ``csrc/crf.hip``): ``batches`` serves the split once more in the
+    order it was predicted in; per batch ``guide(batch["image"])`` -- a ``SpectralProjection`` with at most three outputs, or any
+    callable that returns ``(N, K, h, w)`` (or ``(N, 1, K, h, w)``) with K <= 3, ``None`` for no guide -- is the appearance feature of a
+    mean-field refinement of the stored binary logits (``**crf``: ``radius``, ``iterations``, ``theta_alpha``, ``theta_beta``,
+    ``theta_gamma``, ``w_appearance``, ``w_smooth``, ``compat``).  Returns a new ``SplitPrediction`` with the refined logits
+    ``L_1 - L_0`` and the same masks, offsets, sizes and names; ``spread`` is carried over."""
+    from .crf import MAX_GUIDES, dense_crf
+    if "output" in crf:
+        raise ValueError("crf_split: it stores output='logit'; output is not its to take")
+    if getattr(guide, "out_channels", 0) > MAX_GUIDES:
+        raise ValueError(f"crf_split: the guide has {guide.out_channels} outputs, the CRF takes at most {MAX_GUIDES}")
+    logits: List[torch.Tensor] = []
+    i = 0
+    with torch.inference_mode():
+        for batch in batches:
+            image = batch["image"]
+            _require_cuda(image, "evaluation image")
+            n, (h, w) = int(image.shape[0]), (int(image.shape[-2]), int(image.shape[-1]))
+            if i + n > len(pred):
+                raise ValueError("crf_split: the batches hold more images than the stored prediction")
+            if _names(batch.get("index"), n) != pred.names[i:i + n] or any(s != (h, w) for s in pred.sizes[i:i + n]):
+                raise ValueError(f"crf_split: images {i}..{i + n - 1} are not the ones the prediction stored (serve the split in "
+                                 "the same order, unshuffled)")
+            a, b = pred.offsets[i], pred.offsets[i + n]
+            g = None if guide is None else guide(image)
+            logits.append(dense_crf(pred.logits[a:b].view(n, h, w), g, output="logit", **crf).reshape(-1))
+            i += n
+    if i != len(pred):
+        raise ValueError(f"crf_split: the batches held {i} of the {len(pred)} stored images")
+    return SplitPrediction(torch.cat(logits), pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
+
+
 def ridge_split(batches: Iterable[dict], plane, sigmas, **ridge) -> SplitPrediction:
     """``detect_split`` for the classical spatial baseline (``hyperpri_amd.ridge_filter``, ``csrc/ridge.hip``): per batch
     ``plane(batch["image"])`` -- a ``SpectralProjection``, or any callable that returns ``(N, 1 or T, h, w)`` (or ``(N, 1, T, h, w)``),

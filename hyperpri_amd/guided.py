@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._args import FILTER_DOMAINS, _filter_args, _p, _stream
+from ._args import FILTER_DOMAINS, _filter_args, _guide_frame, _p, _stream
 
 MAX_RADIUS = 8              # hpri_guided_max_radius
 MAX_GUIDES = 3              # hpri_guided_max_guides
@@ -89,13 +89,7 @@ def guided_filter(guide: torch.Tensor, maps: torch.Tensor, radius: int, eps: flo
             raise ValueError(f"guided_filter: the {what} must be a tensor, got {type(t).__name__}")
         if t.dtype != torch.float32:
             raise ValueError(f"guided_filter: need float32 {what}, got {t.dtype}")
-    g = guide
-    if g.dim() == 5:
-        if g.shape[1] != 1:
-            raise ValueError(f"guided_filter: a 5-d guide must be (N, 1, K, h, w), got {tuple(g.shape)}")
-        g = g[:, 0]
-    if g.dim() != 4 or not 1 <= int(g.shape[1]) <= MAX_GUIDES:
-        raise ValueError(f"guided_filter: need a guide (N, K, h, w) or (N, 1, K, h, w) with K in [1, {MAX_GUIDES}], got {tuple(guide.shape)}")
+    g = _guide_frame(guide, MAX_GUIDES, "guided_filter")
     N, K, h, w = (int(s) for s in g.shape)
     if maps.dim() not in (3, 4) or (int(maps.shape[0]), int(maps.shape[-2]), int(maps.shape[-1])) != (N, h, w):
         raise ValueError(f"guided_filter: need maps (N, h, w) or (N, T, h, w) on the guide's frame {(N, h, w)}, got {tuple(maps.shape)}")

@@ -1027,6 +1027,54 @@ int hpri_guided_coeffs(const float* guide, int gs, int K, const float* maps, int
 int hpri_guided_apply(const float* guide, int gs, int K, int N, int T, int H, int W, int radius, int domain, const void* workspace,
                       size_t workspace_bytes, float* out, hipStream_t stream);
 
+/* ---- dense CRF: windowed mean-field refinement of score maps (crf.hip; hyperpri_amd/crf.py) ---------------------------------------
+ * Mean-field inference in the fully connected CRF of Kraehenbuehl and Koltun restricted to a (2 radius + 1)^2 window (the convolutional
+ * CRF of Teichmann and Cipolla), exact inside the window.  Forward only.
+ *   unary   fp32 logits (N, C, H, W), 2 <= C <= hpri_crf_max_classes (8); binary = 1 (C must be 2): fp32 logits z (N, H, W), DEFINED as
+ *           the two-class problem U = (0, z).
+ *   guide   fp32 channels-last (N, H, W, gs), the first K channels are read, 0 <= K <= hpri_crf_max_guides (3), K <= gs (the layouts of
+ *           hpri_guided_coeffs).  K = 0: no guide (the pointer may be NULL), and then w_a must be 0.
+ *   1 <= radius <= hpri_crf_max_radius (8), 1 <= iterations <= hpri_crf_max_iterations (16).
+ *   host constants, made in fp64 and rounded once to fp32 (hyperpri_amd.crf.crf_tables), host memory:
+ *           ta[d] = exp(-d^2 / (2 theta_alpha^2)), tg[d] = exp(-d^2 / (2 theta_gamma^2)) for d = 0 .. radius (1 everywhere for an
+ *           infinite theta), b = 1 / (2 theta_beta^2) > 0; weights w_a, w_s >= 0, finite.
+ *   compat  NULL: Potts, mu(l, l') = -[l = l'].  Else a host-side fp32 C x C matrix, row-major, finite.
+ * Per image, all in fp32 in this order:
+ *   Q^0 = softmax(U);  softmax(L): e_l = expf(L_l - max L), the e_l summed in class order from the first, then Q_l = e_l / sum.
+ *   for t = 1 .. iterations, per pixel i: the neighbours j = i + (dy, dx), dy ascending from -radius, dx ascending inside a row, the
+ *   centre (0, 0) skipped; a neighbour outside the image contributes +0.0 (its Q is +0.0), so a pixel's result depends only on its
+ *   neighbourhood and its distance to the borders.  Per neighbour:
+ *       s = fmaf(dI_c, dI_c, s) from 0 over c = 0 .. K-1 ascending,  dI_c = I_j,c - I_i,c;   e = expf(-(s * b))   (K = 0: e = 1)
+ *       ga = (w_a * ta[|dy|]) * ta[|dx|],  gs_ = (w_s * tg[|dy|]) * tg[|dx|], each product rounded;   k = fmaf(ga, e, gs_)
+ *       M_l = fmaf(k, Q^(t-1)_j(l), M_l) from 0, for every class l
+ *   m_l = M_l / (float)(n - 1), n the in-image pixels of the clipped window (its extents on the two axes multiplied); n = 1: m_l = 0.
+ *   (The centre is skipped because a pixel's own belief is no message to itself -- mean field sums over j != i; n - 1 is the number of
+ *   messages, so that w_a and w_s mean the same at a border, in a corner and inside.)
+ *   L_l = U_l - p_l,  p_l = fmaf(mu(l, l'), m_l', p_l) from 0 over l' ascending;  Potts: L_l = U_l + m_l (the same value).
+ *   Q^t = softmax(L).
+ *   output 0 (logit): out = the last L, (N, C, H, W); binary: out = L_1 - L_0 (one fp32 subtraction), (N, H, W).
+ *   output 1 (prob):  out = Q^iterations, (N, C, H, W); binary: Q_1, (N, H, W).
+ * One launch per iteration -- no other launch, no host synchronisation, no upload: the tables, mu and the scalars are kernel arguments --
+ * over two ping-pong copies of Q in workspace: hpri_crf_workspace_bytes(N, C, H, W) = 8 N C H W bytes (0 for sizes outside the limits:
+ * C in [2, 8], H W < 2^31, N C H W < 2^40), 4-byte aligned, a pure host query; not touched (may be NULL) with iterations = 1.  A workgroup
+ * owns a tile of hpri_crf_tile_h x hpri_crf_tile_w pixels, one lane a pixel, with the halo of the guide and of all C planes of Q in LDS;
+ * the first launch forms softmax(U) while it fills LDS.  The kernel weights k are recomputed every iteration.  No atomics: the result
+ * of a pixel depends on its neighbourhood and its distance to the image borders, not on N, the grid, the tile or its place in a tile;
+ * identical arguments give identical bits.  Argument errors (a null pointer, a size < 1, C outside [2, 8], binary with C != 2, K outside
+ * [0, 3], gs < K, a radius outside [1, 8], iterations outside [1, 16], a table that does not start at 1 or rises or is negative or NaN,
+ * a weight that is negative or not finite, b not positive and finite with K > 0, w_a != 0 with K = 0, a compat entry that is not finite,
+ * an output other than 0 or 1, a workspace that is too small, a misaligned pointer) return -1 before any launch. */
+int hpri_crf_max_radius(void);
+int hpri_crf_max_classes(void);
+int hpri_crf_max_guides(void);
+int hpri_crf_max_iterations(void);
+int hpri_crf_tile_h(void);
+int hpri_crf_tile_w(void);
+size_t hpri_crf_workspace_bytes(int N, int C, int H, int W);
+int hpri_dense_crf(const float* unary, int binary, const float* guide, int gs, int K, int N, int C, int H, int W, int radius,
+                   int iterations, const float* ta, const float* tg, float b, float w_a, float w_s, const float* compat, int output,
+                   void* workspace, size_t workspace_bytes, float* out, hipStream_t stream);
+
 /* ---- ridge filter: multi-scale Hessian vesselness for thin roots (ridge.hip; hyperpri_amd/ridge.py) -----------------------------
  * A scale-normalised Hessian ridge measure (after Frangi et al. and Sato et al.) of T >= 1 fp32 planes on an (N, H, W) frame.  Pixel
  * (y, x) of plane t of image n is maps[n image_stride + t plane_stride + (y W + x) pixel_stride] (strides in floats, pixel_stride >= 1):
