@@ -7,7 +7,8 @@ from .cache import (CubeAugment, CubeCache, CubeDeform, deform_entries, elastic_
                     plan_epoch_deformed)
 from .cluster import (ClusterSums, SpectralKMeans, assign_reference, cluster_step, cluster_step_reference, kmeans_reference,  # noqa: F401
                       merge_cluster_sums)
-from .crf import DenseCRF, crf_bound, crf_bruteforce, crf_reference, crf_tables, dense_crf  # noqa: F401
+from .crf import (CRFLayer, DenseCRF, crf_backward_reference, crf_bound, crf_bruteforce, crf_grad_bound, crf_layer,  # noqa: F401
+                  crf_reference, crf_tables, dense_crf)
 from .components import (TILE_H, TILE_W, clean_mask, clean_reference, component_table, components_reference,  # noqa: F401
                          label_components)
 from .detect import SpectralDetector, detect_reference, whitener_reference  # noqa: F401
@@ -16,7 +17,7 @@ from .distance import (boundary_reference, centerline_counts, centerline_from_co
                        surface_hist_reference, surface_metrics_from_hist, thin_reference)
 from .evaluate import (CLEAN_LOGIT, SplitPrediction, centerline_metrics, clean_prediction, cluster_split, color_classmaps, color_segmaps,  # noqa: F401
                        default_class_palette, detect_split, evaluate_multiclass, object_metrics, predict_split, surface_metrics, test_net, tta_merge,
-                       crf_split, enhance_split, refine_split, ridge_split, unmix_split, validate_net, write_segmaps, write_spreadmaps)
+                       crf_split, enhance_split, fit_crf, refine_split, ridge_split, unmix_split, validate_net, write_segmaps, write_spreadmaps)
 from .evaluate import root_traits as split_root_traits  # noqa: F401  (``root_traits`` is the per-tensor call of distance.py)
 from .guided import GuidedFilter, guided_bound, guided_bruteforce, guided_filter, guided_reference  # noqa: F401
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401

@@ -17,72 +17,23 @@
 // weights k are recomputed every iteration; the spatial tables, mu and the scalars travel in the kernel's arguments (a workgroup copies
 // a given mu behind its planes in LDS once, so that the C^2 values occupy no registers).  A pixel's M_l sits in registers for all C
 // classes at once: no class grouping, no atomics.
-#include "tail_helpers.h"
-
-#define CRF_TILE_H 16
-#define CRF_TILE_W 32
-#define CRF_THREADS (CRF_TILE_H * CRF_TILE_W)
-#define CRF_MAX_R 8
-#define CRF_MAX_K 3
-#define CRF_MAX_C 8
-#define CRF_MAX_T 16
-#define CRF_PER_CU 2                         // workgroups a CU is offered (what its LDS holds at r = 8); the kernel strides over the rest
-
-struct CrfArgs {
-  const float* unary;      // (N, C, H, W), or (N, H, W) with binary
-  const float* guide;      // (N, H, W, gs)
-  const float* qin;        // (N, C, H, W): Q^(t-1); not read by the first launch
-  float* qout;             // (N, C, H, W): Q^t; not written by the last launch
-  float* out;              // the last launch writes
-  long long items;         // tiles x images
-  float ta[CRF_MAX_R + 1], tg[CRF_MAX_R + 1];
-  float mu[CRF_MAX_C * CRF_MAX_C];
-  float b, wa, ws;
-  int gs, vec, N, H, W, r, tiles_x, tiles_y, binary, potts, first, last, output;
-};
-
-// in-image pixels of the window of coordinate v on an axis of length L
-__device__ __forceinline__ int crf_extent(int v, int r, int L) { return min(v + r, L - 1) - max(v - r, 0) + 1; }
-
-// e_l = expf(L_l - max L), summed in class order, one division per class
-template <int C>
-__device__ __forceinline__ void crf_softmax(const float (&L)[C], float (&Q)[C]) {
-  float mx = L[0];
-#pragma unroll
-  for (int l = 1; l < C; ++l) mx = fmaxf(mx, L[l]);
-  float sum = 0.f;
-#pragma unroll
-  for (int l = 0; l < C; ++l) {
-    Q[l] = expf(L[l] - mx);
-    sum += Q[l];
-  }
-#pragma unroll
-  for (int l = 0; l < C; ++l) Q[l] = Q[l] / sum;
-}
-
-template <int C>
-__device__ __forceinline__ void crf_unary(const CrfArgs& g, int n, long long hw, long long px, float (&U)[C]) {
-  if (C == 2 && g.binary) {
-    U[0] = 0.f;
-    U[1] = g.unary[n * hw + px];
-  } else {
-#pragma unroll
-    for (int l = 0; l < C; ++l) U[l] = g.unary[((long long)n * C + l) * hw + px];
-  }
-}
+#include "crf_common.h"
 
 template <int K, int C>
 __global__ __launch_bounds__(CRF_THREADS) void crf_iter_kernel(const CrfArgs g) {
   extern __shared__ __align__(16) float crf_lds[];
   const int r = g.r, lw = CRF_TILE_W + 2 * r, plane = lw * (CRF_TILE_H + 2 * r);
   const long long hw = (long long)g.H * g.W;
+  const bool vec = g.flags & CRF_VEC, binary = g.flags & CRF_BINARY, potts = g.flags & CRF_POTTS, first = g.flags & CRF_FIRST,
+             last = g.flags & CRF_LAST, prob = g.flags & CRF_PROB;
   float* __restrict__ mu = crf_lds + (K + C) * plane;            // C x C behind the planes: read from there, not held in registers
-  if (!g.potts)
-    for (int i = threadIdx.x; i < C * C; i += CRF_THREADS) mu[i] = g.mu[i];
-  for (long long item = blockIdx.x; item < g.items; item += gridDim.x) {
-    const int txi = (int)(item % g.tiles_x);
-    const long long rest = item / g.tiles_x;
-    const int tyi = (int)(rest % g.tiles_y), n = (int)(rest / g.tiles_y);
+  if (!potts)
+    for (int i = threadIdx.x; i < C * C; i += CRF_THREADS) mu[i] = g.mu_dev ? g.mu_dev[i] : g.mu[i];
+  const float w_a = g.wa_dev ? *g.wa_dev : g.wa, w_s = g.ws_dev ? *g.ws_dev : g.ws;      // (the training entries: device memory)
+  for (int item = blockIdx.x; item < g.items; item += gridDim.x) {
+    const int txi = item % g.tiles_x;
+    const int rest = item / g.tiles_x;
+    const int tyi = rest % g.tiles_y, n = rest / g.tiles_y;
     const int y0 = tyi * CRF_TILE_H, x0 = txi * CRF_TILE_W;
     for (int idx = threadIdx.x; idx < plane; idx += CRF_THREADS) {
       const int ly = idx / lw, lx = idx - ly * lw;
@@ -94,14 +45,14 @@ __global__ __launch_bounds__(CRF_THREADS) void crf_iter_kernel(const CrfArgs g) 
       for (int l = 0; l < C; ++l) Q[l] = 0.f;
       if (K > 0) {
         float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (in) hpri_load4(g.guide + (n * hw + px) * g.gs, K, g.vec, v);
+        if (in) hpri_load4(g.guide + (n * hw + px) * g.gs, K, vec, v);
 #pragma unroll
         for (int a = 0; a < K; ++a) crf_lds[a * plane + idx] = v[a];
       }
       if (in) {
-        if (g.first) {
+        if (first) {
           float U[C];
-          crf_unary<C>(g, n, hw, px, U);
+          crf_unary<C>(g.unary, binary, n, hw, px, U);
           crf_softmax<C>(U, Q);
         } else {
 #pragma unroll
@@ -121,7 +72,7 @@ __global__ __launch_bounds__(CRF_THREADS) void crf_iter_kernel(const CrfArgs g) 
 #pragma unroll
       for (int l = 0; l < C; ++l) M[l] = 0.f;
       for (int dy = -r; dy <= r; ++dy) {
-        const float war = g.wa * g.ta[abs(dy)], wsr = g.ws * g.tg[abs(dy)];
+        const float war = w_a * g.ta[abs(dy)], wsr = w_s * g.tg[abs(dy)];
         for (int dx = -r; dx <= r; ++dx) {
           if (dy == 0 && dx == 0) continue;
           const float ga = war * g.ta[abs(dx)], gs_ = wsr * g.tg[abs(dx)];
@@ -141,10 +92,10 @@ __global__ __launch_bounds__(CRF_THREADS) void crf_iter_kernel(const CrfArgs g) 
       const int cnt = crf_extent(y, r, g.H) * crf_extent(x, r, g.W);
       const long long px = (long long)y * g.W + x;
       float U[C], L[C];
-      crf_unary<C>(g, n, hw, px, U);
+      crf_unary<C>(g.unary, binary, n, hw, px, U);
 #pragma unroll
       for (int l = 0; l < C; ++l) M[l] = cnt > 1 ? M[l] / (float)(cnt - 1) : 0.f;
-      if (g.potts) {
+      if (potts) {
 #pragma unroll
         for (int l = 0; l < C; ++l) L[l] = U[l] + M[l];
       } else {
@@ -156,8 +107,8 @@ __global__ __launch_bounds__(CRF_THREADS) void crf_iter_kernel(const CrfArgs g) 
           L[l] = U[l] - p;
         }
       }
-      if (g.last && g.output == 0) {
-        if (C == 2 && g.binary) {
+      if (last && !prob) {
+        if (C == 2 && binary) {
           g.out[n * hw + px] = L[1] - L[0];
         } else {
 #pragma unroll
@@ -166,10 +117,10 @@ __global__ __launch_bounds__(CRF_THREADS) void crf_iter_kernel(const CrfArgs g) 
       } else {
         float Q[C];
         crf_softmax<C>(L, Q);
-        if (g.last && C == 2 && g.binary) {
+        if (last && C == 2 && binary) {
           g.out[n * hw + px] = Q[1];
         } else {
-          float* __restrict__ dst = g.last ? g.out : g.qout;
+          float* __restrict__ dst = last ? g.out : g.qout;
 #pragma unroll
           for (int l = 0; l < C; ++l) dst[((long long)n * C + l) * hw + px] = Q[l];
         }
@@ -186,11 +137,6 @@ extern "C" int hpri_crf_max_guides(void) { return CRF_MAX_K; }
 extern "C" int hpri_crf_max_iterations(void) { return CRF_MAX_T; }
 extern "C" int hpri_crf_tile_h(void) { return CRF_TILE_H; }
 extern "C" int hpri_crf_tile_w(void) { return CRF_TILE_W; }
-
-static inline bool crf_frame_ok(int N, int C, int H, int W) {
-  return N > 0 && C >= 2 && C <= CRF_MAX_C && H > 0 && W > 0 && (long long)H * W < (1LL << 31) && (long long)N * C < (1LL << 31) &&
-         (long long)N * C * H * W < (1LL << 40);
-}
 
 extern "C" size_t hpri_crf_workspace_bytes(int N, int C, int H, int W) {
   if (!crf_frame_ok(N, C, H, W)) return 0;
@@ -216,11 +162,33 @@ static inline void crf_launch_classes(const CrfArgs& g, int C, int blocks, size_
   }
 }
 
-static inline bool crf_unit_table(const float* t, int r) {      // exp(-d^2 / (2 theta^2)): 1 at d = 0, in [0, 1] and not increasing
-  if (t[0] != 1.f) return false;
-  for (int d = 1; d <= r; ++d)
-    if (!(t[d] >= 0.f && t[d] <= t[d - 1])) return false;
-  return true;
+// The geometry, the tables and the launches the plain and the training forward share.  q[t] is where iteration t + 1 writes Q^(t+1)
+// and where iteration t + 2 reads it.  The last iteration writes out; with keep_last it writes Q^T into q[T - 1] as every other does.
+static int crf_run(CrfArgs& g, int K, int N, int C, int binary, int output, int radius, int iterations, const float* ta, const float* tg,
+                   bool compat, float* const* q, bool keep_last, hipStream_t stream) {
+  for (int d = 0; d <= radius; ++d) {
+    g.ta[d] = ta[d];
+    g.tg[d] = tg[d];
+  }
+  g.r = radius; g.tiles_x = hpri_cdiv(g.W, CRF_TILE_W); g.tiles_y = hpri_cdiv(g.H, CRF_TILE_H);
+  g.items = (int)((long long)g.tiles_x * g.tiles_y * N);
+  const int flags = (K > 0 && g.gs % 4 == 0 && hpri_aligned16(g.guide) ? CRF_VEC : 0) | (binary ? CRF_BINARY : 0) | (compat ? 0 : CRF_POTTS) |
+                    (output ? CRF_PROB : 0);
+  const size_t lds = crf_plane_lds(radius, K, C) + (compat ? (size_t)C * C * sizeof(float) : 0);
+  const int blocks = hpri_grid_per_cu(g.items, 1, CRF_PER_CU);
+  for (int t = 0; t < iterations; ++t) {
+    g.flags = flags | (t == 0 ? CRF_FIRST : 0) | (t == iterations - 1 && !keep_last ? CRF_LAST : 0);
+    g.qin = t == 0 ? nullptr : q[t - 1];
+    g.qout = q[t];
+    switch (K) {
+      case 0: crf_launch_classes<0>(g, C, blocks, lds, stream); break;
+      case 1: crf_launch_classes<1>(g, C, blocks, lds, stream); break;
+      case 2: crf_launch_classes<2>(g, C, blocks, lds, stream); break;
+      default: crf_launch_classes<3>(g, C, blocks, lds, stream); break;
+    }
+    HPRI_CHECK_LAUNCH();
+  }
+  return HPRI_OK;
 }
 
 extern "C" int hpri_dense_crf(const float* unary, int binary, const float* guide, int gs, int K, int N, int C, int H, int W, int radius,
@@ -246,29 +214,62 @@ extern "C" int hpri_dense_crf(const float* unary, int binary, const float* guide
       g.mu[i] = compat[i];
     }
   }
-  for (int d = 0; d <= radius; ++d) {
-    g.ta[d] = ta[d];
-    g.tg[d] = tg[d];
-  }
   g.unary = unary; g.guide = guide; g.out = out; g.b = K > 0 ? b : 0.f; g.wa = w_a; g.ws = w_s;
-  g.gs = gs; g.vec = K > 0 && gs % 4 == 0 && hpri_aligned16(guide); g.N = N; g.H = H; g.W = W; g.r = radius;
-  g.tiles_x = hpri_cdiv(W, CRF_TILE_W); g.tiles_y = hpri_cdiv(H, CRF_TILE_H); g.binary = binary; g.potts = compat == nullptr;
-  g.output = output; g.items = (long long)g.tiles_x * g.tiles_y * N;
-  const size_t lds = (size_t)(CRF_TILE_W + 2 * radius) * (CRF_TILE_H + 2 * radius) * (K + C) * sizeof(float) +
-                     (compat ? (size_t)C * C * sizeof(float) : 0);
-  const int blocks = hpri_grid_per_cu(g.items, 1, CRF_PER_CU);
-  float* q[2] = {(float*)workspace, (float*)workspace + (size_t)N * C * H * W};
-  for (int t = 0; t < iterations; ++t) {
-    g.first = t == 0; g.last = t == iterations - 1;
-    g.qin = g.first ? nullptr : q[(t - 1) & 1];
-    g.qout = g.last ? nullptr : q[t & 1];
-    switch (K) {
-      case 0: crf_launch_classes<0>(g, C, blocks, lds, stream); break;
-      case 1: crf_launch_classes<1>(g, C, blocks, lds, stream); break;
-      case 2: crf_launch_classes<2>(g, C, blocks, lds, stream); break;
-      default: crf_launch_classes<3>(g, C, blocks, lds, stream); break;
-    }
-    HPRI_CHECK_LAUNCH();
+  g.gs = gs; g.H = H; g.W = W;
+  float* q[CRF_MAX_T];
+  for (int t = 0; t < iterations; ++t) q[t] = t == iterations - 1 ? nullptr : (float*)workspace + (size_t)(t & 1) * N * C * H * W;
+  return crf_run(g, K, N, C, binary, output, radius, iterations, ta, tg, compat != nullptr, q, false, stream);
+}
+
+// ---- the training forward: the same kernel, the weights from device memory, Q^1 .. Q^(T-1) (and Q^T under output prob) kept ---------
+extern "C" size_t hpri_crf_train_workspace_bytes(int N, int C, int H, int W, int T) {
+  if (!crf_frame_ok(N, C, H, W) || T < 1 || T > CRF_MAX_T) return 0;
+  return crf_train_partials(N, C, H, W, T) * sizeof(double) + (size_t)(T + 2) * N * C * H * W * sizeof(float);
+}
+
+extern "C" int hpri_dense_crf_train_forward(const float* unary, int binary, const float* guide, int gs, int K, int N, int C, int H, int W,
+                                            int radius, int iterations, const float* ta, const float* tg, float b, const float* w_a,
+                                            const float* w_s, const float* compat, int output, int keep, void* workspace,
+                                            size_t workspace_bytes, float* out, hipStream_t stream) {
+  HPRI_REQUIRE(unary && ta && tg && out && w_s, "dense_crf_train_forward: null pointer");
+  HPRI_REQUIRE(crf_frame_ok(N, C, H, W), "dense_crf_train_forward: bad sizes (N, H, W >= 1, C in [2, hpri_crf_max_classes])");
+  HPRI_REQUIRE(binary == 0 || (binary == 1 && C == 2), "dense_crf_train_forward: binary must be 0, or 1 with C = 2");
+  HPRI_REQUIRE(K >= 0 && K <= CRF_MAX_K, "dense_crf_train_forward: K must lie in [0, hpri_crf_max_guides]");
+  HPRI_REQUIRE(K == 0 || (guide && gs >= K && w_a), "dense_crf_train_forward: a guide needs a pointer, a channel stride of at least K and w_a");
+  HPRI_REQUIRE(radius >= 1 && radius <= CRF_MAX_R, "dense_crf_train_forward: the radius must lie in [1, hpri_crf_max_radius]");
+  HPRI_REQUIRE(iterations >= 1 && iterations <= CRF_MAX_T, "dense_crf_train_forward: the iterations must lie in [1, hpri_crf_max_iterations]");
+  HPRI_REQUIRE(crf_unit_table(ta, radius) && crf_unit_table(tg, radius),
+               "dense_crf_train_forward: a spatial table must start at 1 and fall to no less than 0");
+  HPRI_REQUIRE(K == 0 || (b > 0.f && b <= 3.0e38f), "dense_crf_train_forward: b must be positive and finite");
+  HPRI_REQUIRE(output == 0 || output == 1, "dense_crf_train_forward: output must be 0 (logit) or 1 (prob)");
+  HPRI_REQUIRE(keep == 0 || keep == 1, "dense_crf_train_forward: keep must be 0 or 1");
+  HPRI_REQUIRE(keep ? (workspace && workspace_bytes >= hpri_crf_train_workspace_bytes(N, C, H, W, iterations))
+                    : (iterations == 1 || (workspace && workspace_bytes >= hpri_crf_workspace_bytes(N, C, H, W))),
+               "dense_crf_train_forward: the workspace is too small");
+  HPRI_REQUIRE((((uintptr_t)unary | (uintptr_t)guide | (uintptr_t)out | (uintptr_t)w_a | (uintptr_t)w_s | (uintptr_t)compat) & 3) == 0 &&
+                   ((uintptr_t)workspace & 7) == 0, "dense_crf_train_forward: misaligned pointer");
+  CrfArgs g = {};
+  g.unary = unary; g.guide = guide; g.out = out; g.b = K > 0 ? b : 0.f;
+  g.wa_dev = K > 0 ? w_a : nullptr; g.wa = 0.f;                  // (no guide: no appearance kernel, w_a is not read)
+  g.ws_dev = w_s; g.mu_dev = compat;
+  g.gs = gs; g.H = H; g.W = W;
+  const size_t set = (size_t)N * C * H * W;
+  float* q[CRF_MAX_T];
+  if (keep) {
+    float* stack = (float*)((double*)workspace + crf_train_partials(N, C, H, W, iterations));
+    for (int t = 0; t < iterations; ++t) q[t] = t == iterations - 1 && output == 0 ? nullptr : stack + (size_t)t * set;
+  } else {
+    for (int t = 0; t < iterations; ++t) q[t] = t == iterations - 1 ? nullptr : (float*)workspace + (size_t)(t & 1) * set;
   }
+  // Under output prob the backward starts from Q^T (both planes of a binary input): the last iteration writes it into the stack as
+  // every other does, and out is a copy of it (binary: of plane 1 of every image).
+  const bool keep_last = keep && output == 1;
+  const int rc = crf_run(g, K, N, C, binary, output, radius, iterations, ta, tg, compat != nullptr, q, keep_last, stream);
+  if (rc != HPRI_OK || !keep_last) return rc;
+  const float* qT = q[iterations - 1];
+  const size_t hw = (size_t)H * W * sizeof(float);
+  const hipError_t e = binary ? hipMemcpy2DAsync(out, hw, qT + (size_t)H * W, 2 * hw, hw, N, hipMemcpyDeviceToDevice, stream)
+                              : hipMemcpyAsync(out, qT, set * sizeof(float), hipMemcpyDeviceToDevice, stream);
+  if (e != hipSuccess) return hpri_set_error(HPRI_ERR_LAUNCH, hipGetErrorString(e));
   return HPRI_OK;
 }

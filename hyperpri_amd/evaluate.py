@@ -363,6 +363,54 @@ def crf_split(pred: SplitPrediction, batches: Iterable[dict], guide, **crf) -> S
     return SplitPrediction(torch.cat(logits), pred.masks, list(pred.offsets), list(pred.sizes), list(pred.names), pred.spread)
 
 
+def fit_crf(pred: SplitPrediction, batches: Iterable[dict], guide, layer, steps: int, lr: float, loss=None):
+    """Fit a ``hyperpri_amd.CRFLayer`` (``output="logit"``) to a stored split, in place: ``steps`` steps of the package's fused Adam at
+    ``lr`` on ``loss`` (default: its ``BCEWithLogitsLoss``) between ``layer(stored logits, guide)`` and the stored masks, the mean over
+    the split's pixels.  ``batches`` serves the split ONCE, as for ``crf_split``, for ``guide(batch["image"])`` alone (``None``: a layer
+    without a guide); the guide maps stay in HBM and every step runs on them.  ``crf_split`` with the extra state of
+    ``layer.frozen()`` (without ``output``) evaluates the result."""
+    from .crf import MAX_GUIDES, CRFLayer
+    from .losses import BCEWithLogitsLoss
+    from .optim import FusedAdam
+    if not isinstance(layer, CRFLayer):
+        raise ValueError(f"fit_crf: the layer must be a CRFLayer (CRFLayer.from_crf makes one of a DenseCRF), got {type(layer).__name__}")
+    if isinstance(steps, bool) or int(steps) != steps or int(steps) < 1:
+        raise ValueError(f"fit_crf: steps must be a positive integer, got {steps!r}")
+    if layer.output != "logit":
+        raise ValueError("fit_crf: the layer must have output='logit' (the stored masks are compared with logits)")
+    if getattr(guide, "out_channels", 0) > MAX_GUIDES:
+        raise ValueError(f"fit_crf: the guide has {guide.out_channels} outputs, the CRF takes at most {MAX_GUIDES}")
+    parts = []
+    i = 0
+    with torch.no_grad():                              # (not inference_mode: the guide maps are saved for the backward)
+        for batch in batches:
+            image = batch["image"]
+            _require_cuda(image, "evaluation image")
+            n, (h, w) = int(image.shape[0]), (int(image.shape[-2]), int(image.shape[-1]))
+            if i + n > len(pred):
+                raise ValueError("fit_crf: the batches hold more images than the stored prediction")
+            if _names(batch.get("index"), n) != pred.names[i:i + n] or any(s != (h, w) for s in pred.sizes[i:i + n]):
+                raise ValueError(f"fit_crf: images {i}..{i + n - 1} are not the ones the prediction stored (serve the split in the same "
+                                 "order, unshuffled)")
+            parts.append((pred.offsets[i], pred.offsets[i + n], (n, h, w), None if guide is None else guide(image).clone()))
+            i += n
+    if i != len(pred):
+        raise ValueError(f"fit_crf: the batches held {i} of the {len(pred)} stored images")
+    loss = BCEWithLogitsLoss() if loss is None else loss
+    opt = FusedAdam([p for p in layer.parameters() if p.requires_grad], lr=float(lr))
+    total = float(pred.offsets[-1])
+    # (a stored split was made under inference_mode; autograd saves only ordinary tensors)
+    logits, masks = (t.clone() if t.is_inference() else t.detach() for t in (pred.logits, _as_f32(pred.masks)))
+    with torch.enable_grad():
+        for _ in range(int(steps)):
+            opt.zero_grad(set_to_none=True)
+            for a, b, shape, g in parts:
+                part = loss(layer(logits[a:b].view(shape), g), masks[a:b].view(shape))
+                (part * ((b - a) / total)).backward()
+            opt.step()
+    return layer
+
+
 def ridge_split(batches: Iterable[dict], plane, sigmas, **ridge) -> SplitPrediction:
     """``detect_split`` for the classical spatial baseline (``hyperpri_amd.ridge_filter``, ``csrc/ridge.hip``): per batch
     ``plane(batch["image"])`` -- a ``SpectralProjection``, or any callable that returns ``(N, 1 or T, h, w)`` (or ``(N, 1, T, h, w)``),

@@ -1075,6 +1075,59 @@ int hpri_dense_crf(const float* unary, int binary, const float* guide, int gs, i
                    int iterations, const float* ta, const float* tg, float b, float w_a, float w_s, const float* compat, int output,
                    void* workspace, size_t workspace_bytes, float* out, hipStream_t stream);
 
+/* ---- trainable dense CRF: the backward through the mean-field iterations (crf.hip, crf_grad.hip; hyperpri_amd/crf.py) --------------
+ * Gradients through hpri_dense_crf's T iterations to the unaries, w_a, w_s and the compatibility matrix mu; not to the guide or thetas.
+ * In both entries w_a, w_s and compat are DEVICE pointers (one fp32 each; compat a row-major C x C matrix, NULL: Potts; w_a may be NULL
+ * and is not read with K = 0), so that a training step has no host synchronisation and no upload.  They accept any finite value -- a
+ * negative weight is a repulsive CRF, not an error; the host cannot check device values, a NaN or an infinity there gives NaN.
+ *
+ * hpri_dense_crf_train_forward: hpri_dense_crf's kernel and launches with the weights read from device memory; out is bit-identical to
+ * hpri_dense_crf at the same parameter values.  keep = 0: nothing is kept, workspace as for hpri_dense_crf (two ping-pong plane sets,
+ * untouched with iterations = 1).  keep = 1: workspace is the training workspace below, and iteration t writes Q^t into slot t - 1 of
+ * its stack where the plain forward ping-pongs -- Q^1 .. Q^(T-1), and under output 1 also Q^T (both planes of a binary input; out is
+ * then a device copy of it, of plane 1 for a binary input); there is no second pass over the window.  Q^0 = softmax(U) and, under output 0, nothing of iteration T is needed by the backward.
+ *
+ * hpri_crf_train_workspace_bytes(N, C, H, W, T): 8 T tiles (2 + C^2) + 4 (T + 2) N C H W bytes, tiles = N ceil(H / 16) ceil(W / 32): the
+ * fp64 partial sums, the stack of T plane sets and two plane sets of gL; 8-byte aligned; 0 for sizes outside the limits or T outside
+ * [1, 16]; a pure host query.  The backward reads the stack the forward of the same arguments wrote into the same workspace.
+ *
+ * hpri_dense_crf_backward, with g = grad_out in the output's shape; all fp32 in this order unless said otherwise:
+ *   gL^T:  output 0: gL^T = g; binary: (-g, +g).  output 1: gv = g (binary: gv = (0, g)), d = fmaf(Q^T_l, gv_l, d) from 0 over l ascending,
+ *          gL^T_l = Q^T_l * (gv_l - d).
+ *   for t = T .. 1, per pixel j (one launch per t, the forward's tile, one lane a pixel):
+ *     gU_j:  t = T: gU_j = gL^T_j; else gU_j = gU_j + gL^t_j; at t = 1 then gU_j = gU_j + gL^0_j -- the order t = T, T-1, .., 0, by the lane
+ *            that owns the pixel.
+ *     b_i(l) = gL^t_i(l) / (float)(n_i - 1), n_i the in-image pixels of pixel i's clipped window; n_i = 1: 0; i outside the image: +0.0.
+ *     the window of j in the forward's order (dy ascending, dx ascending inside a row, the centre skipped), i = j + (dy, dx):
+ *       s, e as the forward forms them for pixel j and neighbour i (s from dI_c = I_i,c - I_j,c; e = expf(-(s * b)))
+ *       ka = (ta[|dy|] * ta[|dx|]) * e,  ps = tg[|dy|] * tg[|dx|], each product rounded
+ *       GA_l = fmaf(ka, b_i(l), GA_l),  GS_l = fmaf(ps, b_i(l), GS_l) from 0       (K = 0: no GA and no exponential)
+ *     H_l = fmaf(w_a, GA_l, w_s * GS_l)   (K = 0: H_l = w_s * GS_l)
+ *     gQ_l' = -p_l',  p_l' = fmaf(mu(l, l'), H_l, p_l') from 0 over l ascending   (mu transposed; Potts: gQ_l = H_l)
+ *     with Q = Q^(t-1)_j (t = 1: softmax(U_j) formed again, the forward's bits):
+ *       d = fmaf(Q_l, gQ_l, d) from 0 over l ascending;   gL^(t-1)_j(l) = Q_l * (gQ_l - d)
+ *     parameters, per pixel: a_l' = -(fmaf(mu(l, l'), GA_l, .) over l ascending) (Potts: GA_l'), A_j = fmaf(a_l', Q_l', A_j) from 0 over l'
+ *       ascending; S_j likewise from GS; M_j(l, l') = -(H_l * Q_l').
+ *   grad_w_a = sum A_j, grad_w_s = sum S_j, grad_compat(l, l') = sum M_j(l, l') over all pixels and iterations: the family's reduction
+ *   rule -- every per-pixel value converted to fp64, summed per TILE AND ITERATION by the halving tree over the tile's 512 lanes (a lane
+ *   outside the image adds 0), then one block of 256 threads adds the partial sums in fp64: the T x tiles sums taken in the order t
+ *   descending from T, the tile index (image, tile row, tile column) ascending inside a t; thread j adds entries j, j + 256, .. of that
+ *   sequence in that order, the halving tree adds the 256 threads' sums, and the total rounds once to fp32.  The sums do not depend on
+ *   the grid.  No floating-point atomic anywhere.
+ *   grad_unary in the unaries' shape (binary: gz = gU_1, (N, H, W)); grad_w_a, grad_w_s (one fp32 each) and grad_compat (C x C) are device
+ *   pointers, each may be NULL (not wanted); grad_compat needs compat, grad_w_a needs K > 0.
+ * Identical arguments give identical bits.  LDS: 8 KB for the sums and the forward's planes, with b where it holds Q.  Argument errors (as hpri_dense_crf's, without the checks of the weights' values; a workspace that is too small or
+ * not 8-byte aligned; grad_compat without compat; grad_w_a with K = 0) return -1 before any launch. */
+size_t hpri_crf_train_workspace_bytes(int N, int C, int H, int W, int T);
+int hpri_dense_crf_train_forward(const float* unary, int binary, const float* guide, int gs, int K, int N, int C, int H, int W, int radius,
+                                 int iterations, const float* ta, const float* tg, float b, const float* w_a, const float* w_s,
+                                 const float* compat, int output, int keep, void* workspace, size_t workspace_bytes, float* out,
+                                 hipStream_t stream);
+int hpri_dense_crf_backward(const float* grad_out, const float* unary, int binary, const float* guide, int gs, int K, int N, int C, int H,
+                            int W, int radius, int iterations, const float* ta, const float* tg, float b, const float* w_a,
+                            const float* w_s, const float* compat, int output, void* workspace, size_t workspace_bytes, float* grad_unary,
+                            float* grad_w_a, float* grad_w_s, float* grad_compat, hipStream_t stream);
+
 /* ---- ridge filter: multi-scale Hessian vesselness for thin roots (ridge.hip; hyperpri_amd/ridge.py) -----------------------------
  * A scale-normalised Hessian ridge measure (after Frangi et al. and Sato et al.) of T >= 1 fp32 planes on an (N, H, W) frame.  Pixel
  * (y, x) of plane t of image n is maps[n image_stride + t plane_stride + (y W + x) pixel_stride] (strides in floats, pixel_stride >= 1):

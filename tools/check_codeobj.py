@@ -41,7 +41,7 @@ HOT = (
     "bn_", "col_", "maxpool2", "nchw_to_nhwc", "outconv", "bce_", "adam", "copy_slice", "fill_pad", "to_planes",
     "cube_gather_kernel", "mask_gather_kernel", "cube_warp_kernel", "mask_warp_kernel", "cube_deform_kernel", "mask_deform_kernel", "elastic_field_kernel", "seg_loss_", "tta_merge_",
     "band_moments_kernel", "band_gram_kernel", "band_project_kernel", "band_affine_kernel", "band_assign_kernel", "band_cluster_kernel",
-    "band_unmix_kernel", "band_extreme_kernel", "guided_coeff_kernel", "guided_apply_kernel", "ridge_filter_kernel", "crf_iter_kernel",
+    "band_unmix_kernel", "band_extreme_kernel", "guided_coeff_kernel", "guided_apply_kernel", "ridge_filter_kernel", "crf_iter_kernel", "crf_back_kernel",
     "soft_skel_fwd_kernel", "soft_skel_bwd_kernel", "cldice_finalize_kernel", "centerline_count_kernel",
     "sort_hist_kernel", "sort_count_kernel", "sort_scan_kernel", "sort_scatter_kernel", "sort_finish_kernel", "lz_", "rk_",
 )
@@ -182,7 +182,7 @@ def run(force=False):
     out = {"stamp": stamp, "kernels": rows, "hot_path_kernels_with_spills": bad, "ok": not bad}
     os.makedirs(B.LIBDIR, exist_ok=True)
     with open(cache, "w") as fh:
-        json.dump(out, fh)
+        json.dump(out, fh, separators=(",", ":"))
     return out
 
 
