@@ -17,9 +17,11 @@ from .distance import (boundary_reference, centerline_counts, centerline_from_co
                        surface_hist_reference, surface_metrics_from_hist, thin_reference)
 from .evaluate import (CLEAN_LOGIT, SplitPrediction, centerline_metrics, clean_prediction, cluster_split, color_classmaps, color_segmaps,  # noqa: F401
                        default_class_palette, detect_split, evaluate_multiclass, object_metrics, predict_split, surface_metrics, test_net, tta_merge,
-                       crf_split, enhance_split, fit_crf, refine_split, ridge_split, unmix_split, validate_net, write_segmaps, write_spreadmaps)
+                       crf_split, enhance_split, fit_crf, gmm_split, refine_split, ridge_split, unmix_split, validate_net, write_segmaps, write_spreadmaps)
 from .evaluate import root_traits as split_root_traits  # noqa: F401  (``root_traits`` is the per-tensor call of distance.py)
 from .guided import GuidedFilter, guided_bound, guided_bruteforce, guided_filter, guided_reference  # noqa: F401
+from .mixture import (GmmOperands, GmmSums, SpectralGMM, gmm_bound, gmm_classes_reference, gmm_operands, gmm_reference,  # noqa: F401
+                      gmm_score_reference, gmm_step, gmm_step_reference, gmm_sums_bound, merge_gmm_sums)
 from .model_parts import DoubleConv, Down, OutConv, Up, set_precision  # noqa: F401
 from .models import (CubeNET, SpectralUNET, UNet, initialize_model, set_parameter_requires_grad,  # noqa: F401
                      translate_load_dir)

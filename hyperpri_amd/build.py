@@ -17,7 +17,7 @@ LIBDIR = os.path.join(HERE, "lib")
 # fp32 / bf16 / bf16x3 / bf16x6) and libhyperpri_hip_f16.so (-DHPRI_H16_F16: IEEE half, precision mode "f16"; csrc/common.h).
 LIB = os.path.join(LIBDIR, "libhyperpri_hip.so")
 LIB_F16 = os.path.join(LIBDIR, "libhyperpri_hip_f16.so")
-SOURCES = ["api.cpp", "conv_fwd.hip", "conv_bf16v3.hip", "gemm_bf16v3.hip", "gemm_f32v2.hip", "wgrad_bf16v3.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wgrad.hip", "conv_wgrad_bf16v2.hip", "pack.hip", "bn.hip", "elementwise.hip", "step.hip", "ingest.hip", "conv_ingest.hip", "cache.hip", "cache_warp.hip", "cache_deform.hip", "segmap.hip", "multiclass.hip", "segloss.hip", "tta.hip", "components.hip", "distance.hip", "spectral.hip", "skeleton.hip", "detect.hip", "cluster.hip", "sort.hip", "unmix.hip", "guided.hip", "ridge.hip", "crf.hip", "crf_grad.hip"]
+SOURCES = ["api.cpp", "conv_fwd.hip", "conv_bf16v3.hip", "gemm_bf16v3.hip", "gemm_f32v2.hip", "wgrad_bf16v3.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wgrad.hip", "conv_wgrad_bf16v2.hip", "pack.hip", "bn.hip", "elementwise.hip", "step.hip", "ingest.hip", "conv_ingest.hip", "cache.hip", "cache_warp.hip", "cache_deform.hip", "segmap.hip", "multiclass.hip", "segloss.hip", "tta.hip", "components.hip", "distance.hip", "spectral.hip", "skeleton.hip", "detect.hip", "cluster.hip", "mixture.hip", "sort.hip", "unmix.hip", "guided.hip", "ridge.hip", "crf.hip", "crf_grad.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 

@@ -288,6 +288,18 @@ def cluster_split(model: nn.Module, batches: Iterable[dict]) -> SplitPrediction:
         return store.result("cluster_split")
 
 
+def gmm_split(model: nn.Module, batches: Iterable[dict]) -> SplitPrediction:
+    """``cluster_split`` for a Gaussian mixture classifier (``hyperpri_amd.SpectralGMM`` with two classes): per batch the model's
+    ``"logit"`` map -- the log posterior odds of the foreground -- is stored as ``logits``, with masks, offsets, sizes and names exactly as
+    ``predict_split`` stores them, so the evaluation functions read a statistical baseline unchanged."""
+    store = _SplitStore()
+    with torch.inference_mode():
+        for batch in batches:
+            image, _ = _checked_batch(batch)
+            store.add_scores(model(image, output="logit")[:, 0], batch)
+        return store.result("gmm_split")
+
+
 def unmix_split(model: nn.Module, batches: Iterable[dict], mode: str = "fcls") -> SplitPrediction:
     """``cluster_split`` for an unmixer (``hyperpri_amd.SpectralUnmixer`` with a foreground endmember): per batch the model's ``"logit"``
     map under ``mode`` -- the logit of every pixel's foreground abundance -- is stored as ``logits``, with masks, offsets, sizes and

@@ -940,6 +940,51 @@ int hpri_band_cluster_sums(const void* cache, int cache_dtype, int slots, int Hs
                            void* workspace, size_t workspace_bytes, long long* counts, double* sums, double* totals,
                            hipStream_t stream);
 
+/* ---- spectral Gaussian mixtures: scores and the E-step with the M-step's sums (mixture.hip; hyperpri_amd/mixture.py) ---------------
+ * K <= hpri_band_gmm_max_components (8) Gaussians with full covariances in a shared projection to q <= hpri_band_gmm_max_dims (32)
+ * dimensions; component k belongs to class classes[k] < C <= 8.  cs % 8 == 0 and cs <= hpri_band_max_cs; qp = roundup(q, 8).
+ *   d[c]   = fp32(x[c] - pivot[c]), as hpri_band_assign rounds it; pivot: fp32 (cs), zero pad entries; NULL: d = x
+ *   z[i]   = fmaf(weight[i][cs-1], d[cs-1], ... fmaf(weight[i][0], d[0], 0))      i < q: bitwise the chain of hpri_band_project from a
+ *            zero bias; weight (qp, cs) fp32, zero pad rows and columns
+ *   u_k[i] = fmaf(A[k][i][qp-1], z[qp-1], ... fmaf(A[k][i][0], z[0], a[k][i]))    A (K, qp, qp), a (K, qp) fp32, zero pad entries.  For a
+ *            covariance Sigma_k = L_k L_k^T and a mean m_k the caller passes A_k = L_k^-1 and a_k = -A_k m_k
+ *   m_k    = sum_i u_k[i]^2: with s_g = fmaf(u[i], u[i], s_g) from 0 over the rows i = 4 g + j (j = 0..3), then 16 + 4 g + j where
+ *            qp > 16, of group g < 4, m_k = (s_0 + s_1) + (s_2 + s_3)
+ *   l_k    = fmaf(-0.5, m_k, c[k]); c (K) fp32 = log pi_k - sum log diag L_k - (q / 2) log 2 pi, rounded once
+ *   L_c    = mx + logf(sum expf(l_k - mx)), mx = max l_k, over the components k of class c in ascending k (a class without a
+ *            component: -inf); L_all: the same over all k < K;  r_k = expf(l_k - mx) / sum_j expf(l_j - mx) over all j < K in
+ *            ascending j: exp(l_k - L_all), and exactly 1 / n among n identical components
+ *   hpri_band_gmm_score  x: the zero-padded channels-last fp32 batch (pixels, cs) hpri_band_assign takes, read as pixels / plane
+ *                        images of `plane` pixels; classes: K ints in HOST memory.  Outputs, each may be NULL but not all (one that is
+ *                        not asked for is not touched): loglik (images, C, plane) fp32 = L_c; logit (pixels) fp32 = L_1 - L_0, C == 2
+ *                        only, not clamped; labels (pixels) uint8 = the lowest c < C with L_c == max, < C for every input; resp
+ *                        (images, K, plane) fp32 = r_k; nll (pixels) fp32 = -L_all.  One pass; weight and A stay in LDS (a tile of 64
+ *                        pixels beside them, 32 where both do not fit); nothing of size pixels x K q leaves the workgroup.
+ *   hpri_band_gmm_sums   over the selected pixels of the listed slots (the leading arguments of hpri_band_cluster_sums), with
+ *                        e_k = fp32(z - means[k]) (means (K, qp) fp32): *count (int64); N[k] = sum r_k; S[k*qp + i] = sum r_k e_k[i];
+ *                        Q[(k*qp + i)*qp + j] = sum r_k e_k[i] e_k[j]; *LL = sum L_all (fp64; entries with i or j >= q: 0).
+ *     Summation, as hpri_band_cluster_sums: inside a run of hpri_band_fp32_run pixels every sum is the fp32 chain
+ *     acc = fmaf(fp32(r_k X[i]), X[j], acc) from 0 over ALL the run's pixels in ascending order (v_mfma_f32_32x32x2_f32, k = pixel),
+ *     X = (e_k[0..q-1], 1): Q = (i, j), S = (i, q), N = (q, q); at q == 32, N = fmaf(r_k, 1, acc), S[i] = fmaf(fp32(r_k e_k[i]), 1, acc)
+ *     for i < 31 and S[31] = fmaf(r_k, e_k[31], acc).  A pixel that is not selected has r_k = 0.  Runs go into
+ *     hpri_band_gmm_parts() = 256 fp64 partials in run order, a finishing kernel adds those in ascending order; L_all is added in fp64
+ *     per pixel slot of a chunk, as zmin there.  No floating-point atomic.  workspace: hpri_band_gmm_workspace_bytes(cs, q, K) bytes,
+ *     16-byte aligned; a pure function of its arguments (0 for a cs, q or K the pass does not take).
+ * Argument errors (a null pointer, a size <= 0, pixels % plane != 0, a bad cs, q, K or C, a class outside [0, C), logit with C != 2, no
+ * output at all, a select or dtype out of range, a selection without masks, a short workspace, a misaligned pointer) return -1
+ * before any launch. */
+int hpri_band_gmm_max_components(void);
+int hpri_band_gmm_max_dims(void);
+int hpri_band_gmm_parts(void);
+size_t hpri_band_gmm_workspace_bytes(int cs, int q, int K);
+int hpri_band_gmm_score(const float* x, long long pixels, long long plane, int cs, const float* pivot, const float* weight, int q,
+                        const float* A, const float* a, const float* c, const int* classes, int K, int C, float* loglik, float* logit,
+                        unsigned char* labels, float* resp, float* nll, hipStream_t stream);
+int hpri_band_gmm_sums(const void* cache, int cache_dtype, int slots, int Hs, int Ws, int cs, const unsigned char* masks,
+                       const int* slot_table, int n, int select, const float* pivot, const float* weight, int q, const float* A,
+                       const float* a, const float* c, const float* means, int K, void* workspace, size_t workspace_bytes,
+                       long long* count, double* N, double* S, double* Q, double* LL, hipStream_t stream);
+
 /* ---- spectral unmixing: abundance maps and ATGP endmembers (unmix.hip; hyperpri_amd/unmix.py) ------------------------------------
  * The linear mixing model x ~ E a with M <= hpri_band_unmix_max_members (8) endmembers E (C, M).  The host fits in fp64 and rounds
  * once: E = Q R, the thin QR with a positive diagonal of R.  x: the zero-padded channels-last fp32 batch (pixels, cs) of

@@ -40,7 +40,7 @@ HOT = (
     "conv_fwd_kernel", "conv_wgrad_kernel", "splitk_finish_kernel", "wgrad_reduce", "conv_wino6", "wino6",
     "bn_", "col_", "maxpool2", "nchw_to_nhwc", "outconv", "bce_", "adam", "copy_slice", "fill_pad", "to_planes",
     "cube_gather_kernel", "mask_gather_kernel", "cube_warp_kernel", "mask_warp_kernel", "cube_deform_kernel", "mask_deform_kernel", "elastic_field_kernel", "seg_loss_", "tta_merge_",
-    "band_moments_kernel", "band_gram_kernel", "band_project_kernel", "band_affine_kernel", "band_assign_kernel", "band_cluster_kernel",
+    "band_moments_kernel", "band_gram_kernel", "band_project_kernel", "band_affine_kernel", "band_assign_kernel", "band_cluster_kernel", "band_gmm_score_kernel", "band_gmm_sums_kernel",
     "band_unmix_kernel", "band_extreme_kernel", "guided_coeff_kernel", "guided_apply_kernel", "ridge_filter_kernel", "crf_iter_kernel", "crf_back_kernel",
     "soft_skel_fwd_kernel", "soft_skel_bwd_kernel", "cldice_finalize_kernel", "centerline_count_kernel",
     "sort_hist_kernel", "sort_count_kernel", "sort_scan_kernel", "sort_scatter_kernel", "sort_finish_kernel", "lz_", "rk_",
